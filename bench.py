@@ -6,6 +6,10 @@ Weak scaling: every GPU owns a 512^3 z-slab worth of DoF; the global grid double
 (N=1: 512^3, N=2: 512x512x1024, N=4: 512x1024x1024, N=8: 1024^3 = SURVEY config 4).
 Strong scaling (--scaling strong [--base 512|1024]): the base^3 grid split over all GPUs.
 N > 1 lines carry per-rank halo / allreduce times (per_rank_comm).
+A plain run sets up, warms up, times the K steps and prints the line. --dump-outputs DIR also writes
+what the timed steps computed (residual history, a fixed sample of x) as DIR/*.npy. --full adds,
+after the timed steps, everything else the line can carry: per-kernel diagnostics, the matvec rows,
+the HBM copy probe, the single-reduction variant, the CPU baselines and the secondary workloads.
 Launch: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either under
 torch.distributed.run (one rank per GPU), or plain: with no WORLD_SIZE in the environment
 bench.py starts the N rank processes itself (self_launch: child processes, no exec, before any
@@ -67,6 +71,7 @@ def cg_iter_bytes(defer, pstore=1):
         return pb_["a"] + pb_["b_x"][0]
     return pb_["a"] + ((defer - 1) * pb_["b_even"] + pb_["b_x"][defer]) / defer
 SEED = 20231015
+DUMP_DOUBLES = 1 << 20       # --dump-outputs keeps at most this many values of x (8 MiB)
 SECONDARY_TIMEOUT_STATUS = 3  # exit status when the secondary workloads' watchdog fires
 
 
@@ -133,6 +138,49 @@ def run_sr_variant(args, pb, ctx, A, P, b, da, dist, world):
             "bytes_per_dof": iter_bytes,
             "achieved_GBps": iter_bytes * nloc / per_step / 1e9 if nloc else None,
             "passes": passes, "its": its, "rnorm_last": float(hist[-1])}
+
+
+def timed_iterations(args, ctx, ksp, b, x, dist):
+    """The timed region of the headline: args.steps CG iterations of the solve `ksp` has begun
+    (warm-up done), device sync at the end, then the barriers and KSP end. rtol = atol = 0, so the
+    solve normally never stops by itself; if it does (a breakdown once the residual sits at the
+    rounding floor, after thousands of steps) the same solve is begun again and the remaining
+    steps are timed too, so --steps is the number of timed iterations whatever its size.
+    Returns (seconds, reason, its, history) -- the last three as the solve's caller gets them."""
+    elapsed, done, before = 0.0, 0, args.warmup
+    while True:
+        t0 = time.perf_counter()
+        ksp.iterate(args.steps - done)
+        ctx.sync()
+        elapsed += time.perf_counter() - t0
+        ctx.barrier()
+        if dist:
+            dist.barrier()
+        reason, its, hist = ksp.end()
+        ran = min(int(its) - before, args.steps - done)
+        done += max(ran, 0)
+        if done >= args.steps:
+            return elapsed, reason, its, hist
+        if ran <= 0 and before == 0:
+            sys.exit(f"bench: the solve stops at once (KSP reason {reason}); "
+                     f"{done} of {args.steps} steps timed")
+        ksp.begin(b, x)
+        before = 0
+
+
+def dump_outputs(dirname, rank, world, x, hist):
+    """--dump-outputs: what the caller of the timed path holds after its last step -- the residual
+    history (rank 0) and this rank's part of x, float64. A vector longer than its share of
+    DUMP_DOUBLES is written as a fixed sample (indices drawn from SEED, sorted), so the files
+    stay far below 64 MB in all and two builds can be compared value for value."""
+    os.makedirs(dirname, exist_ok=True)
+    xs = np.asarray(x.get_values(), dtype=np.float64).reshape(-1)
+    keep = DUMP_DOUBLES // world
+    if xs.size > keep:
+        xs = xs[np.sort(np.random.default_rng(SEED).integers(0, xs.size, keep))]
+    np.save(os.path.join(dirname, "x.npy" if world == 1 else f"x_rank{rank}.npy"), xs)
+    if rank == 0:
+        np.save(os.path.join(dirname, "residual_history.npy"), np.asarray(hist, np.float64))
 
 
 def global_grid(ngpus, base=512):
@@ -426,17 +474,19 @@ def run_solve_workload(args, pb, ctx, workload, scaling, steps, warmup, rank, wo
     elapsed = t1 - t0
     ms_roof, cnt_roof = ctx.timing(roof)
     ctx.set_timing(False)
-    # diagnostics: one more solve with every phase timed
-    ctx.set_timing(True)
-    ctx.reset_timing()
-    ksp.solve(b, x)
-    ctx.sync()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, x, hist)
+    if args.full:  # diagnostics: one more solve with every phase timed
+        ctx.set_timing(True)
+        ctx.reset_timing()
+        ksp.solve(b, x)
+        ctx.sync()
     nloc = da.nlocal
     kern = {}
     comm = {"rank": rank, "device": ctx_device(ctx), "transport": comm_transport,
             "comm_nranks": comm_nranks}
     for nm, bpd in W["kernels"].items():
-        ms_, cnt_ = ctx.timing(nm)
+        ms_, cnt_ = ctx.timing(nm) if args.full else (0.0, 0)
         if cnt_ == 0:
             continue
         row = {"avg_ms": ms_ / cnt_, "launches_per_solve": cnt_}
@@ -538,7 +588,8 @@ def run_solve_workload(args, pb, ctx, workload, scaling, steps, warmup, rank, wo
                 out["roofline"]["traffic_source"] = tr[key][roof].get("source")
         except Exception:
             pass
-        if world == 1 and not args.no_cpu_baseline and args.cpu_baseline != "none":
+        if (args.full and world == 1 and not args.no_cpu_baseline
+                and args.cpu_baseline != "none"):
             out["cpu_baseline"] = cpu_solve_baseline(workload, cpu_budget_s)
     for o in (ksp, r, xt, x, b):
         o.destroy()
@@ -550,7 +601,7 @@ def run_solve_workload(args, pb, ctx, workload, scaling, steps, warmup, rank, wo
 
 
 def run_secondary(args, pb, ctx, rank, world, dist, comm_transport, comm_nranks, holder, json_fd):
-    """The default run (star7-jacobi headline) also measures the solve workloads -- config 5
+    """The --full run (star7-jacobi headline) also measures the solve workloads -- config 5
     (compact-fft, 512^3 strong-scaled) and star7-mg -- so every N of a scaling run records them
     beside the headline, under "secondary". A watchdog bounds them (PB_BENCH_SECONDARY_TIMEOUT_S,
     default 240 s): if they do not finish, rank 0 prints the headline line with the error and the
@@ -575,6 +626,7 @@ def run_secondary(args, pb, ctx, rank, world, dist, comm_transport, comm_nranks,
     timer.daemon = True
     timer.start()
     sec = {}
+    args = argparse.Namespace(**dict(vars(args), dump_outputs=None))  # the headline's stay
     for wl, steps, warmup in (("compact-fft", 10, 2), ("star7-mg", 3, 1)):
         try:
             res = run_solve_workload(args, pb, ctx, wl, SOLVE_WORKLOADS[wl]["scaling"], steps,
@@ -729,8 +781,15 @@ def main():
                     help="A/B runs: name=value[,name=value] tuning settings (pb_tune_set, "
                          "INTEGRATION.md) applied before the run")
     ap.add_argument("--secondary", type=int, choices=(0, 1), default=1,
-                    help="default run: also measure the compact-fft (config 5) and star7-mg "
+                    help="--full run: also measure the compact-fft (config 5) and star7-mg "
                          "solve workloads after the headline, under \"secondary\" (1, default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: per-kernel "
+                         "diagnostics, the matvec rows, the HBM copy probe, the single-reduction "
+                         "variant, the CPU baselines and the secondary solve workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (residual history, a fixed sample "
+                         "of x) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     # --scaling defaults to the workload's own (config 5 is a strong-scaling case)
     if args.scaling is None:
@@ -820,89 +879,119 @@ def main():
     roof = "cg_pass_b_even" if (pstore and defer == 4) else "cg_pass_a"
     ctx.set_timing(True, only=roof, every=4)
     ctx.reset_timing()
-    t0 = time.perf_counter()
-    ksp.iterate(args.steps)
-    ctx.sync()
-    t1 = time.perf_counter()
-    ctx.barrier()
-    if dist:
-        dist.barrier()
-    elapsed = t1 - t0
+    elapsed, reason, its, hist = timed_iterations(args, ctx, ksp, b, x, dist)
     ms_roof, cnt_roof = ctx.timing(roof)
     ctx.set_timing(False)
-    # per-kernel diagnostics of the other passes: a few more iterations, every launch timed
-    ctx.set_timing(True)
-    ctx.reset_timing()
-    ksp.iterate(diag_steps)
-    ctx.sync()
-    ms_b, cnt_b = ctx.timing(PASS_B_X_NAME[defer])
-    for d_, nm in PASS_B_X_NAME.items():  # the library's deferral depth, from the pass it ran
-        if cnt_b == 0 and ctx.timing(nm)[1] > 0:
-            defer = d_
-            ms_b, cnt_b = ctx.timing(nm)
-    ms_be, cnt_be = ctx.timing("cg_pass_b_even")
-    ms_a, cnt_a = ctx.timing("cg_pass_a")
-    # per-rank communication in the diagnostic iterations: the halo exchange on the comm stream
-    # (overlapped with pass A's interior planes), the two scalar allreduces per iteration, and
-    # pass A including its wait for the halo
-    comm = {"rank": rank, "iterations": diag_steps, "device": device,
-            "transport": comm_transport, "comm_nranks": comm_nranks, "comm_rank": comm_rank}
-    for nm in ("halo_comm", "allreduce", "cg_pass_a", "halo"):
-        ms_, cnt_ = ctx.timing(nm)
-        comm[f"{nm}_ms_per_iter"] = ms_ / diag_steps
-        comm[f"{nm}_calls"] = cnt_
-    ctx.set_timing(False)
-    reason, its, hist = ksp.end()
-    per_rank = [comm]
     if dist:
         import torch
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, comm)
-
-    # standalone matvec timing (north-star target kernel), outside the timed CG region
-    y = pb.Vec(da)
-    for _ in range(3):
-        A.mult(x, y)
-    ctx.sync()
-    ctx.set_timing(True)
-    ctx.reset_timing()
-    for _ in range(args.matvecs):
-        A.mult(x, y)
-    ctx.sync()
-    ms_mv, cnt_mv = ctx.timing("stencil")
-    # sustained: SURVEY §8(d) (i)'s 100 back-to-back matvecs, HIP events around each launch; the
-    # first and last ten show whether the rate drifts under sustained load (clocks, heat)
-    ctx.reset_timing()
-    for _ in range(args.sustained):
-        A.mult(x, y)
-    ctx.sync()
-    mv_s = ctx.timing_samples("stencil")
-    ctx.set_timing(False)
-    # HBM calibration in this same process: a flat copy of the matvec's
-    # bytes, so a slow-mode box shows up as a slow copy too
-    try:
-        cp_best, cp_med = ctx.copy_probe(n=nloc_even(da.nlocal), reps=10)
-    except Exception:
-        cp_best = cp_med = None
-    sr_var = run_sr_variant(args, pb, ctx, A, P, b, da, dist, world)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, x, hist)
 
     nloc = da.nlocal
     N = n[0] * n[1] * n[2]
-    t_b = ms_b / max(cnt_b, 1) / 1e3
-    t_be = ms_be / max(cnt_be, 1) / 1e3
-    t_a = ms_a / max(cnt_a, 1) / 1e3
     t_roof = ms_roof / max(cnt_roof, 1) / 1e3  # inside the timed region
-    if roof == "cg_pass_a":
-        t_a = t_roof
-    else:
-        t_be = t_roof
     PB = PASS_BYTES[pstore]
     roof_bytes = PB["a"] if roof == "cg_pass_a" else PB["b_even"]
-    t_mv = ms_mv / max(cnt_mv, 1) / 1e3
     gbs = lambda bytes_per_dof, t: bytes_per_dof * nloc / t / 1e9 if t > 0 else 0.0
+
+    full = None
+    if args.full:
+        # per-kernel diagnostics of the other passes: a few iterations of the same solve begun
+        # again, every launch timed
+        ksp.begin(b, x)
+        ctx.set_timing(True)
+        ctx.reset_timing()
+        ksp.iterate(diag_steps)
+        ctx.sync()
+        ms_b, cnt_b = ctx.timing(PASS_B_X_NAME[defer])
+        for d_, nm in PASS_B_X_NAME.items():  # the library's deferral depth, from the pass it ran
+            if cnt_b == 0 and ctx.timing(nm)[1] > 0:
+                defer = d_
+                ms_b, cnt_b = ctx.timing(nm)
+        ms_be, cnt_be = ctx.timing("cg_pass_b_even")
+        ms_a, cnt_a = ctx.timing("cg_pass_a")
+        # per-rank communication in the diagnostic iterations: the halo exchange on the comm
+        # stream (overlapped with pass A's interior planes), the two scalar allreduces per
+        # iteration, and pass A including its wait for the halo
+        comm = {"rank": rank, "iterations": diag_steps, "device": device,
+                "transport": comm_transport, "comm_nranks": comm_nranks, "comm_rank": comm_rank}
+        for nm in ("halo_comm", "allreduce", "cg_pass_a", "halo"):
+            ms_, cnt_ = ctx.timing(nm)
+            comm[f"{nm}_ms_per_iter"] = ms_ / diag_steps
+            comm[f"{nm}_calls"] = cnt_
+        ctx.set_timing(False)
+        ksp.end()
+        per_rank = [comm]
+        if dist:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, comm)
+
+        # standalone matvec timing (north-star target kernel), outside the timed CG region
+        y = pb.Vec(da)
+        for _ in range(3):
+            A.mult(x, y)
+        ctx.sync()
+        ctx.set_timing(True)
+        ctx.reset_timing()
+        for _ in range(args.matvecs):
+            A.mult(x, y)
+        ctx.sync()
+        ms_mv, cnt_mv = ctx.timing("stencil")
+        # sustained: SURVEY §8(d) (i)'s 100 back-to-back matvecs, HIP events around each launch;
+        # the first and last ten show whether the rate drifts under sustained load (clocks, heat)
+        ctx.reset_timing()
+        for _ in range(args.sustained):
+            A.mult(x, y)
+        ctx.sync()
+        mv_s = ctx.timing_samples("stencil")
+        ctx.set_timing(False)
+        y.destroy()
+        # HBM calibration in this same process: a flat copy of the matvec's
+        # bytes, so a device in a slow mode shows up as a slow copy too
+        try:
+            cp_best, cp_med = ctx.copy_probe(n=nloc_even(da.nlocal), reps=10)
+        except Exception:
+            cp_best = cp_med = None
+        sr_var = run_sr_variant(args, pb, ctx, A, P, b, da, dist, world)
+
+        t_b = ms_b / max(cnt_b, 1) / 1e3
+        t_be = ms_be / max(cnt_be, 1) / 1e3
+        t_a = ms_a / max(cnt_a, 1) / 1e3
+        if roof == "cg_pass_a":
+            t_a = t_roof
+        else:
+            t_be = t_roof
+        t_mv = ms_mv / max(cnt_mv, 1) / 1e3
+        full = {
+            # the north-star kernel (standalone 7-point matvec, 16 B/DoF) and this process's
+            # flat-copy calibration of the same bytes, in the roofline object
+            "roofline": {"matvec_ms": t_mv * 1e3,
+                         "matvec_frac": gbs(MATVEC_BYTES, t_mv) / HBM_PEAK_GBS,
+                         "matvec_sustained_median_ms": sustained_median_ms(mv_s),
+                         "copy_probe_GBps": cp_best, "copy_probe_median_GBps": cp_med,
+                         "copy_probe_frac": (cp_best / HBM_PEAK_GBS) if cp_best else None,
+                         "mclk_MHz": memory_clock()},
+            "kernels": {
+                "cg_pass_a": {"avg_ms": t_a * 1e3, "GBps": gbs(PB["a"], t_a),
+                              "frac": gbs(PB["a"], t_a) / HBM_PEAK_GBS, "bytes_per_dof": PB["a"]},
+                "cg_pass_b_even": {"avg_ms": t_be * 1e3, "GBps": gbs(PB["b_even"], t_be),
+                                   "frac": gbs(PB["b_even"], t_be) / HBM_PEAK_GBS,
+                                   "bytes_per_dof": PB["b_even"]},
+                PASS_B_X_NAME[defer]: {"avg_ms": t_b * 1e3, "GBps": gbs(PB["b_x"][defer], t_b),
+                                       "frac": gbs(PB["b_x"][defer], t_b) / HBM_PEAK_GBS,
+                                       "bytes_per_dof": PB["b_x"][defer]},
+                "matvec_star7": {"avg_ms": t_mv * 1e3, "GBps": gbs(MATVEC_BYTES, t_mv),
+                                 "frac": gbs(MATVEC_BYTES, t_mv) / HBM_PEAK_GBS,
+                                 "dofs_per_s": nloc / t_mv if t_mv > 0 else 0.0,
+                                 "bytes_per_dof": MATVEC_BYTES},
+            },
+            "matvec_star7_sustained": sustained_row(mv_s, nloc, gbs),
+            "variants": {"cg_single_reduction": sr_var},
+            "per_rank_comm": per_rank if world > 1 else None,
+        }
 
     out = None
     if rank == 0:
@@ -942,41 +1031,18 @@ def main():
                          "achieved": gbs(roof_bytes, t_roof), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": gbs(roof_bytes, t_roof) / HBM_PEAK_GBS,
                          "traffic": None, "bytes_per_dof": roof_bytes,
-                         "avg_launch_ms": t_roof * 1e3,
-                         # the north-star kernel (standalone 7-point matvec, 16 B/DoF) and this
-                         # process's flat-copy calibration of the same bytes, in the roofline
-                         # object (the driver keeps it)
-                         "matvec_ms": t_mv * 1e3,
-                         "matvec_frac": gbs(MATVEC_BYTES, t_mv) / HBM_PEAK_GBS,
-                         "matvec_sustained_median_ms": sustained_median_ms(mv_s),
-                         "copy_probe_GBps": cp_best, "copy_probe_median_GBps": cp_med,
-                         "copy_probe_frac": (cp_best / HBM_PEAK_GBS) if cp_best else None,
-                         "mclk_MHz": memory_clock()},
-            "kernels": {
-                "cg_pass_a": {"avg_ms": t_a * 1e3, "GBps": gbs(PB["a"], t_a),
-                              "frac": gbs(PB["a"], t_a) / HBM_PEAK_GBS, "bytes_per_dof": PB["a"]},
-                "cg_pass_b_even": {"avg_ms": t_be * 1e3, "GBps": gbs(PB["b_even"], t_be),
-                                   "frac": gbs(PB["b_even"], t_be) / HBM_PEAK_GBS,
-                                   "bytes_per_dof": PB["b_even"]},
-                PASS_B_X_NAME[defer]: {"avg_ms": t_b * 1e3, "GBps": gbs(PB["b_x"][defer], t_b),
-                                       "frac": gbs(PB["b_x"][defer], t_b) / HBM_PEAK_GBS,
-                                       "bytes_per_dof": PB["b_x"][defer]},
-                "matvec_star7": {"avg_ms": t_mv * 1e3, "GBps": gbs(MATVEC_BYTES, t_mv),
-                                 "frac": gbs(MATVEC_BYTES, t_mv) / HBM_PEAK_GBS,
-                                 "dofs_per_s": nloc / t_mv if t_mv > 0 else 0.0,
-                                 "bytes_per_dof": MATVEC_BYTES},
-            },
-            "matvec_star7_sustained": sustained_row(mv_s, nloc, gbs),
-            "variants": {"cg_single_reduction": sr_var},
+                         "avg_launch_ms": t_roof * 1e3},
             "cg_x_update_every": defer,
             "launcher": os.environ.get("PB_BENCH_LAUNCHER",
                                        "torch.distributed.run" if dist else "none"),
             "transport": comm_transport,
             "rccl_nranks": comm_nranks if comm_transport == "rccl" else None,
-            "per_rank_comm": per_rank if world > 1 else None,
             "ksp_state": {"reason": pb.REASONS.get(reason, reason), "its": its,
                           "rnorm0": float(hist[0]), "rnorm_last": float(hist[-1])},
         }
+        if full:  # --full: the figures of the runs after the timed steps
+            out["roofline"].update(full.pop("roofline"))
+            out.update(full)
         traffic_file = os.path.join(REPO, "profiles", "pmc_traffic.json")
         if os.path.exists(traffic_file):
             try:
@@ -986,18 +1052,19 @@ def main():
                 if key in tr and roof in tr[key]:
                     out["roofline"]["traffic"] = tr[key][roof]["bytes_per_launch"]
                     out["roofline"]["traffic_source"] = tr[key][roof].get("source")
-                for role, kv in out["kernels"].items():
+                for role, kv in out.get("kernels", {}).items():
                     if role in tr.get(key, {}):
                         kv["traffic"] = tr[key][role]["bytes_per_launch"]
             except Exception:
                 pass
-        if world == 1 and not args.no_cpu_baseline and args.cpu_baseline != "none":
+        if (args.full and world == 1 and not args.no_cpu_baseline
+                and args.cpu_baseline != "none"):
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline)
-    for o in (ksp, y, xt, x, b, A, P):
+    for o in (ksp, xt, x, b, A, P):
         o.destroy()
     da.destroy()
     holder = {"out": out if rank == 0 else None}
-    if args.secondary and not args.grid_override:
+    if args.full and args.secondary and not args.grid_override:
         run_secondary(args, pb, ctx, rank, world, dist, comm_transport, comm_nranks, holder,
                       json_fd)
     if rank == 0:

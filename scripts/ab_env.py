@@ -1,5 +1,5 @@
-"""A/B tuning settings on the bench: runs `bench.py --no-cpu-baseline --tune CFG` once per (config, rep),
-interleaved (rep-major) so box drift hits every config alike, and prints one JSON line per run with
+"""A/B tuning settings on the bench: runs `bench.py --full --no-cpu-baseline --tune CFG` once per
+(config, rep), interleaved (rep-major) so drift hits every config alike, and prints one JSON line per run with
 ms/step and the per-kernel averages.
 
 usage: python scripts/ab_env.py REPS 'name=val[,name=val]' ['...' ...] [-- extra bench args]
@@ -20,8 +20,9 @@ for rep in range(reps):
     for cfg in cfgs:
         env = dict(os.environ)
         tune = [] if cfg == "-" else ["--tune", cfg]
-        p = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--no-cpu-baseline",
-                            "--secondary", "0", "--steps", "100", "--warmup", "10"] + tune + extra,
+        p = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--full",
+                            "--no-cpu-baseline", "--secondary", "0", "--steps", "100", "--warmup",
+                            "10"] + tune + extra,
                            env=env, capture_output=True, text=True, timeout=300)
         if p.returncode != 0:
             print(json.dumps({"cfg": cfg, "rep": rep, "rc": p.returncode,

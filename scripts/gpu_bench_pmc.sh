@@ -3,7 +3,7 @@
 set -u
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
-ARGS="--steps 30 --warmup 5 --secondary 0 --cpu-baseline none"
+ARGS="--full --steps 30 --warmup 5 --secondary 0 --cpu-baseline none"
 timeout -k 10 400 python $R/bench.py $ARGS > $R/gpurun_out/bq.json 2> $R/gpurun_out/bq.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp

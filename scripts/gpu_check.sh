@@ -4,6 +4,8 @@
 set -u
 mkdir -p gpurun_out
 ok_or_testfail() { local rc=$1; [ "$rc" -eq 0 ] || [ "$rc" -eq 1 ]; }
+# the bench line with everything beside the headline (diagnostics, baselines, secondaries)
+BENCH_ARGS=${BENCH_ARGS:---full --steps 50 --warmup 5}
 timeout -k 10 ${T_TEST:-900} python -m pytest tests -m gpu -q -rf ${PYTEST_ARGS:-} > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc"; tail -5 gpurun_out/pytest_gpu.log
 ok_or_testfail $rc || exit $rc

@@ -6,7 +6,7 @@ set -u
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r6prof
 mkdir -p $O
-ARGS="--steps 30 --warmup 5 --matvecs 20 --no-cpu-baseline --secondary 0"
+ARGS="--full --steps 30 --warmup 5 --matvecs 20 --no-cpu-baseline --secondary 0"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python3 $R/bench.py $ARGS > $O/bench_prof.json 2> $O/bench_prof.err
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc

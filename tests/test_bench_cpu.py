@@ -112,6 +112,77 @@ def test_solve_workload_dry_run_and_cpu_rows():
         assert cb["kind"] == "port" and cb["cores"] >= 1
 
 
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: the residual history whole, x whole when it is short and otherwise the same
+    sorted sample of DUMP_DOUBLES values every time; float64 .npy files, far below 64 MB."""
+    import os
+
+    import numpy as np
+
+    class Vec:
+        def __init__(self, a):
+            self.a = a
+
+        def get_values(self):
+            return self.a
+
+    hist = np.array([3.0, 2.0, 1.0])
+    small = np.arange(1000.0)
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, Vec(small), hist)
+    assert sorted(os.listdir(tmp_path / "a")) == ["residual_history.npy", "x.npy"]
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), small)
+    assert np.array_equal(np.load(tmp_path / "a" / "residual_history.npy"), hist)
+    big = np.arange(float(3 * bench.DUMP_DOUBLES))
+    bench.dump_outputs(str(tmp_path / "b"), 0, 1, Vec(big), hist)
+    bench.dump_outputs(str(tmp_path / "c"), 0, 1, Vec(big + 0.0), hist)
+    xb, xc = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert xb.dtype == np.float64 and xb.size == bench.DUMP_DOUBLES and np.array_equal(xb, xc)
+    assert np.all(np.diff(xb) >= 0) and xb[-1] > 2.9 * bench.DUMP_DOUBLES  # spread over all of x
+    # N ranks: one file per rank, the same total
+    bench.dump_outputs(str(tmp_path / "d"), 1, 4, Vec(big), hist)
+    assert os.listdir(tmp_path / "d") == ["x_rank1.npy"]
+    assert np.load(tmp_path / "d" / "x_rank1.npy").size == bench.DUMP_DOUBLES // 4
+
+
+def test_timed_iterations_runs_every_step():
+    """--steps is the number of timed iterations: a solve that stops by itself before them is
+    begun again and the rest are run; one that cannot advance is an error, not a short count."""
+    import argparse
+
+    import pytest
+
+    class Ctx:
+        def sync(self):
+            pass
+
+        barrier = sync
+
+    class Ksp:
+        def __init__(self, stop_after, its=0):
+            self.stop_after, self.its, self.asked, self.begins = stop_after, its, [], 0
+
+        def begin(self, b, x):
+            self.begins += 1
+            self.its = 0
+
+        def iterate(self, n):
+            self.asked.append(n)
+            self.its = min(self.its + n, self.stop_after)
+
+        def end(self):
+            return 0, self.its, [1.0] * (self.its + 1)
+
+    args = argparse.Namespace(steps=20, warmup=5)
+    k = Ksp(stop_after=10 ** 9, its=5)
+    el, reason, its, hist = bench.timed_iterations(args, Ctx(), k, None, None, None)
+    assert (k.asked, k.begins, its, len(hist)) == ([20], 0, 25, 26) and el >= 0
+    k = Ksp(stop_after=12, its=5)  # stops after 7 of the 20 timed steps, then every 12
+    _, _, its, _ = bench.timed_iterations(args, Ctx(), k, None, None, None)
+    assert (k.asked, k.begins, its) == ([20, 13, 1], 2, 1)
+    with pytest.raises(SystemExit):
+        bench.timed_iterations(args, Ctx(), Ksp(stop_after=0), None, None, None)
+
+
 def test_dominant_kernel_and_sr_bytes():
     """The solve lines' dominant phase: largest time per solve among the timed kernels, wrappers
     and communication left out; the single-reduction variant's bytes per iteration on one rank

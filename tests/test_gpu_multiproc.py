@@ -141,7 +141,7 @@ def test_bench_solve_workload_self_launch(workload, extra):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PYTHONPATH"] = REPO
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--workload", workload, "--transport", "host"] + extra
+           "--warmup", "1", "--workload", workload, "--transport", "host", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -166,7 +166,7 @@ def test_bench_two_ranks_host_transport():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", "--master-port=29531", os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "6", "--warmup", "2", "--base", "48", "--matvecs", "2",
-           "--transport", "host"]
+           "--transport", "host", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     import json
@@ -174,7 +174,7 @@ def test_bench_two_ranks_host_transport():
     assert len(line) == 1
     d = json.loads(line[0])
     assert d["n_gpus"] == 2 and d["config"]["grid"] == [48, 48, 96] and d["value"] > 0
-    # the default run also measures the solve workloads (config 5 strong-scaled, CG + MG)
+    # the --full run also measures the solve workloads (config 5 strong-scaled, CG + MG)
     sec = d["secondary"]
     assert sec["compact-fft"]["config"]["grid"] == [48, 48, 48]
     assert sec["star7-mg"]["config"]["grid"] == [48, 48, 96]
@@ -184,7 +184,7 @@ def test_bench_two_ranks_host_transport():
 
 
 def test_bench_eight_ranks_default_run_host_transport():
-    """Rehearsal of the driver's N = 8 scaling run on one GPU: `bench.py --gpus 8` with no launcher
+    """Rehearsal of the N = 8 scaling run on one GPU: `bench.py --gpus 8 --full` with no launcher
     (self-launch: 8 rank processes), the default workload plus its secondaries (config 5's compact
     operator with the spectral PC strong-scaled over 8 slabs -- all-to-all transposes on 8 ranks --
     and CG + MG), over the gloo host transport in place of RCCL (which refuses two ranks on one
@@ -195,7 +195,7 @@ def test_bench_eight_ranks_default_run_host_transport():
     env["PYTHONPATH"] = REPO
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "4",
            "--warmup", "1", "--base", "32", "--matvecs", "2", "--sustained", "2",
-           "--transport", "host"]
+           "--transport", "host", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
