@@ -240,6 +240,21 @@ typedef struct {
                         exact arithmetic. Runs as two engine passes on the 7-point operator with
                         -pc_type jacobi|none; with other operators / PCs the KSPSolve_CG iteration
                         runs (default 0) */
+  int initial_guess_nonzero; /* -ksp_initial_guess_nonzero (KSPSetInitialGuessNonzero): the solve
+                        starts from the x passed in, r0 = b - A x0 (x0 is taken as it is: no
+                        null-space projection), and x accumulates onto it. The stopping reference
+                        is then not ||z_0|| but the preconditioned, null-space-removed norm of
+                        the right-hand side ||N(M^-1 b)|| (KSPConvergedDefault), or ||z_0|| when
+                        that is exactly 0; ttol = max(rtol * rnorm0, atol) and the dtol test use
+                        it, pb_ksp_result.rnorm0 reports it; history[0] stays ||z_0|| of the
+                        actual initial residual. 0 (default): x0 = 0, the x passed in is
+                        overwritten */
+  int converged_use_initial_residual_norm; /* -ksp_converged_use_initial_residual_norm
+                        (KSPConvergedDefaultSetUIRNorm): with a nonzero guess the reference is
+                        ||z_0|| of the initial residual (no extra PC application) */
+  int converged_use_min_initial_residual_norm; /* -ksp_converged_use_min_initial_residual_norm
+                        (KSPConvergedDefaultSetUMIRNorm): min(||N(M^-1 b)||, ||z_0||). Setting
+                        both is PB_ERR_ARG, as in PETSc. Neither has an effect without a guess */
 } pb_ksp_opts;
 typedef struct {
   int reason;
@@ -252,7 +267,9 @@ typedef struct {
 int pb_ksp_opts_default(pb_ksp_opts* opts);
 /* Parses PETSc-style options (-ksp_type, -pc_type, -ksp_rtol, -ksp_atol, -ksp_divtol,
  * -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
- * -pc_sor_omega, -ksp_cg_single_reduction [true|false]); unknown options are ignored.
+ * -pc_sor_omega, and the PetscOptionsBool flags -ksp_cg_single_reduction,
+ * -ksp_initial_guess_nonzero, -ksp_converged_use_initial_residual_norm,
+ * -ksp_converged_use_min_initial_residual_norm [true|false]); unknown options are ignored.
  * -pc_type sor: one symmetric red-black SOR sweep (PETSc PCSOR default: 1 local symmetric sweep,
  * here in red-black order). -pc_type mg (or gamg): geometric V(1,1) multigrid with red-black SOR
  * smoothing on the 7-point P (README.md:40-45 recommends GAMG + SOR). Both need even extents. */
@@ -260,12 +277,16 @@ int pb_ksp_opts_parse(pb_ksp_opts* opts, int argc, const char* const* argv);
 
 /* KSPCreate + KSPSetOperators(ksp, A, P) + options. P supplies the Jacobi diagonal. */
 int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** ksp);
-/* KSPSolve(ksp, b, x): x0 = 0 (guess_zero). history (optional, may be NULL): the res->nhist
- * logged norms ||z_k|| (k = 0 .. nhist-1), at most history_cap entries written. */
+/* KSPSolve(ksp, b, x): x0 = 0 (guess_zero; x is overwritten), or x0 = the x passed in with
+ * initial_guess_nonzero (b and x must then be distinct vectors). A KSP may be reused: every
+ * solve reads the flag and x afresh (a time loop warm-starts from the previous step's x).
+ * history (optional, may be NULL): the res->nhist logged norms ||z_k|| (k = 0 .. nhist-1), at
+ * most history_cap entries written. */
 int pb_ksp_solve(pb_ksp* ksp, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
                  int64_t history_cap);
-/* Split form used by benchmarks: setup (r = b, z, ||z0||), then exactly `iters` iterations
- * (continuing from the current state; stopping test applies unless disabled by options). */
+/* Split form used by benchmarks: setup (r = b, or b - A x0 with a nonzero guess; z, ||z0||), then
+ * exactly `iters` iterations (continuing from the current state; stopping test applies unless
+ * disabled by options). */
 int pb_ksp_begin(pb_ksp* ksp, const pb_vec* b, pb_vec* x);
 int pb_ksp_iterate(pb_ksp* ksp, int64_t iters);
 int pb_ksp_end(pb_ksp* ksp, pb_ksp_result* res, double* history, int64_t history_cap);

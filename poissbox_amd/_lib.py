@@ -29,7 +29,9 @@ class KspOpts(C.Structure):
                 ("ksp_type", C.c_int), ("pc_type", C.c_int), ("nullspace", C.c_int),
                 ("monitor", C.c_int), ("converged_reason", C.c_int), ("check_every", C.c_int),
                 ("mg_levels", C.c_int), ("mg_coarse_its", C.c_int), ("sor_omega", c_d),
-                ("cg_single_reduction", C.c_int)]
+                ("cg_single_reduction", C.c_int), ("initial_guess_nonzero", C.c_int),
+                ("converged_use_initial_residual_norm", C.c_int),
+                ("converged_use_min_initial_residual_norm", C.c_int)]
 
 
 class KspResult(C.Structure):

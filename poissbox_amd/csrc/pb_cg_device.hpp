@@ -49,9 +49,17 @@ __device__ __forceinline__ void wave_reduce_parts(const double* __restrict__ par
   }
 }
 
-// stage 0 (after init / the first PC apply): S = (sum t, sum t^2, sum t.r, sum r)
+// how KSPConvergedDefault picks its reference norm when the solve starts from a nonzero guess
+enum { REF_RHS = 0, REF_INITIAL = 1, REF_MIN = 2, REF_ZERO_GUESS = 3 };
+
+// stage 0 (after init / the first PC apply): S = (sum t, sum t^2, sum t.r, sum r).
+// ref = REF_ZERO_GUESS: x0 = 0, the reference norm is ||z_0|| itself. Nonzero guess
+// (KSPConvergedDefault, PETSc): bnorm = ||N(M^-1 b)|| is the reference (REF_RHS; ||z_0|| when it
+// is exactly 0), or ||z_0|| (REF_INITIAL), or the smaller of the two (REF_MIN); the divergence
+// test then applies to ||z_0|| as well (it cannot fire when the reference is ||z_0||)
 __device__ __forceinline__ void cg_stage0(CgState& st, const double* S, double* hist,
-                                          int* h_done) {
+                                          int* h_done, int ref = REF_ZERO_GUESS,
+                                          double bnorm = 0.0) {
   const double N = st.ntot;
   double mu = 0.0, zz = S[1], zr = S[2];
   if (st.nullspace) {
@@ -62,8 +70,11 @@ __device__ __forceinline__ void cg_stage0(CgState& st, const double* S, double* 
   }
   const double dp = norm_from_sq(zz);
   st.mu = mu;
+  double rn0 = dp;
+  if (ref == REF_RHS) rn0 = bnorm == 0.0 ? dp : bnorm;
+  else if (ref == REF_MIN) rn0 = fmin(bnorm, dp);
   st.dp = dp;
-  st.rnorm0 = dp;
+  st.rnorm0 = rn0;
   st.it = 0;
   st.its = 0;
   st.dpi = 0.0;
@@ -79,9 +90,12 @@ __device__ __forceinline__ void cg_stage0(CgState& st, const double* S, double* 
     st.reason = PB_KSP_DIVERGED_NANORINF;
     st.done = 1;
   } else {
-    st.ttol = fmax(st.rtol * dp, st.atol);
+    st.ttol = fmax(st.rtol * rn0, st.atol);
     if (dp <= st.ttol) {
       st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
+      st.done = 1;
+    } else if (ref != REF_ZERO_GUESS && dp >= st.dtol * rn0) {
+      st.reason = PB_KSP_DIVERGED_DTOL;
       st.done = 1;
     } else {
       st.beta = zr;

@@ -116,10 +116,57 @@ __global__ __launch_bounds__(256) void cg_pc_sums_kernel(const double* __restric
   block_sums<4>(acc, parts);
 }
 
+// setup from a nonzero initial guess where no stencil engine forms A x0 (compact / assembled A) or
+// the PC stores z (SOR / MG / FFT): w = A x0 came from the operator; r = b - w, p = 0, x0 left
+// alone. SUMS (Jacobi / no PC): the setup's four sums of s = dinv r and the two of dinv b behind
+// the stopping reference ||N(M^-1 b)||, as the fused pass takes them (GuessInit, pb_stencil.hip)
+template <bool SUMS>
+__global__ __launch_bounds__(256) void cg_guess_resid_kernel(const double* __restrict__ b,
+                                                             const double* __restrict__ w,
+                                                             double* __restrict__ r,
+                                                             double* __restrict__ p, int64_t n,
+                                                             double dinv, double* parts) {
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double bv = b[i];
+    const double rv = bv - w[i];
+    r[i] = rv;
+    p[i] = 0.0;
+    if constexpr (SUMS) {
+      const double s = dinv * rv, sb = dinv * bv;
+      acc[0] += s;
+      acc[1] += s * s;
+      acc[2] += s * rv;
+      acc[3] += rv;
+      acc[4] += sb;
+      acc[5] += sb * sb;
+    }
+  }
+  if constexpr (SUMS) block_sums<6>(acc, parts);
+}
+
 static int gen_blocks(pb_ctx* ctx, int64_t n) {
   int64_t b = (n + 255) / 256;
   const int64_t cap = (int64_t)ctx->num_cus * 8;
   return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
+// nparts != nullptr: with the six sums (dinv as the Jacobi / no-PC setup's), *nparts blocks
+int launch_cg_guess_resid(pb_grid* g, const double* b, const double* w, double* r, double* p,
+                          double dinv, int* nparts) {
+  ScopedTimer tm(g->ctx, "cg_init_guess_vec");
+  const int nb = gen_blocks(g->ctx, g->nlocal);
+  if (nparts) {
+    hipLaunchKernelGGL(cg_guess_resid_kernel<true>, dim3(nb), dim3(256), 0, g->ctx->stream, b, w,
+                       r, p, g->nlocal, dinv, g->ctx->d_partials);
+    *nparts = nb;
+  } else {
+    hipLaunchKernelGGL(cg_guess_resid_kernel<false>, dim3(nb), dim3(256), 0, g->ctx->stream, b, w,
+                       r, p, g->nlocal, dinv, g->ctx->d_partials);
+  }
+  PB_HIP(hipGetLastError());
+  return PB_OK;
 }
 
 int launch_cg_generic_p(pb_grid* g, const double* r, double* p, CgState* st, int first) {

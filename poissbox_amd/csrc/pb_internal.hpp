@@ -324,6 +324,23 @@ struct CgState {
 };
 int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, CgState* st,
                    double dinv, double* hist, int* h_done);
+// Setup from a nonzero initial guess (-ksp_initial_guess_nonzero; x0 is never written):
+//  - fused operator, Jacobi / no PC: one engine pass (pb_stencil.hip GuessInit) reads x0 and b,
+//    stores r = b - A x0 and p = 0, and takes six sums per block (the setup's four of dinv r,
+//    and dinv b, (dinv b)^2) into ctx->d_partials + part_off * 6;
+//  - elsewhere: w = A x0 by the operator, then launch_cg_guess_resid (pb_cg_generic.hip):
+//    r = b - w, p = 0, with the same six sums when nparts != nullptr (Jacobi / no PC).
+// cg_finalize_guess: stage 0 from `width` (6, or 4 with a stored-z PC) sums per block, with
+// KSPConvergedDefault's reference norm: ref 0 = ||N(M^-1 b)|| (from sums 4, 5, or from bsums[0..1]
+// = sum, sum of squares of M^-1 b when width is 4; ||z_0|| if that norm is exactly 0), 1 = ||z_0||,
+// 2 = the smaller of the two.
+int launch_cg_guess_init(pb_grid* g, const Star& s, const double* x0, const double* b, double* r,
+                         double* p, const StencilPlanes& gp, double dinv, int mode, int part_off,
+                         int* nblocks);
+int launch_cg_guess_resid(pb_grid* g, const double* b, const double* w, double* r, double* p,
+                          double dinv, int* nparts);
+int cg_finalize_guess(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
+                      CgState* st, double* hist, int* h_done);
 struct Fold {
   // 0: no fold; 1: stage 1 (pass B); 2: stage 2 (pass A); single-reduction pass P: 3: the
   // residual-sum stage of the previous iteration, then the top of this one; 4: the top only

@@ -45,6 +45,7 @@ struct pb_ksp {
   int fold_nparts_b = 0;     // partial-sum blocks of the last folded pass B
   bool stored_z() const { return mg || fft; }  // PCs whose z = M^-1 r is stored (not Jacobi)
   bool lazy0 = false;  // r0 = b, x0 = 0, p0 = 0 left implicit by pb_ksp_begin
+  double* guess_bsums() const { return reinterpret_cast<double*>(d_st + 2); }
   CgState* d_st = nullptr;
   double* d_hist = nullptr;
   int64_t nhist = 0;
@@ -213,6 +214,18 @@ int pb_ksp_opts_default(pb_ksp_opts* o) {
   o->mg_coarse_its = 8;
   o->sor_omega = 1.0;
   o->cg_single_reduction = 0;
+  o->initial_guess_nonzero = 0;
+  o->converged_use_initial_residual_norm = 0;
+  o->converged_use_min_initial_residual_norm = 0;
+  return PB_OK;
+}
+
+// KSPConvergedDefaultSetUIRNorm / SetUMIRNorm exclude each other (PETSc errors on the second)
+static int check_ref_norm_opts(const pb_ksp_opts* o) {
+  if (o->converged_use_initial_residual_norm && o->converged_use_min_initial_residual_norm)
+    return set_error(PB_ERR_ARG,
+                     "-ksp_converged_use_initial_residual_norm and "
+                     "-ksp_converged_use_min_initial_residual_norm exclude each other");
   return PB_OK;
 }
 
@@ -221,6 +234,18 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
   for (int i = 0; i < argc; ++i) {
     const char* a = argv[i];
     const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+    // PetscOptionsBool: a bare flag is true; an explicit value may follow
+    // (PetscOptionsStringToBool: case-insensitive true/yes/on/1 and false/no/off/0)
+    auto flag = [&](int* out) {
+      auto is = [&](const char* w) { return v && !strcasecmp(v, w); };
+      *out = 1;
+      if (is("true") || is("yes") || is("on") || is("1")) {
+        ++i;
+      } else if (is("false") || is("no") || is("off") || is("0")) {
+        *out = 0;
+        ++i;
+      }
+    };
     if (!strcmp(a, "-ksp_type") && v) {
       if (strcmp(v, "cg")) return set_error(PB_ERR_UNSUPPORTED, "-ksp_type %s: only cg", v);
       o->ksp_type = PB_KSP_CG;
@@ -255,23 +280,20 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
       o->sor_omega = atof(v);
       ++i;
     } else if (!strcmp(a, "-ksp_cg_single_reduction")) {
-      // PetscOptionsBool: a bare flag is true; an explicit value may follow
-      o->cg_single_reduction = 1;
-      // (PetscOptionsStringToBool: case-insensitive true/yes/on/1 and false/no/off/0)
-      auto is = [&](const char* w) { return v && !strcasecmp(v, w); };
-      if (is("true") || is("yes") || is("on") || is("1")) {
-        ++i;
-      } else if (is("false") || is("no") || is("off") || is("0")) {
-        o->cg_single_reduction = 0;
-        ++i;
-      }
+      flag(&o->cg_single_reduction);
+    } else if (!strcmp(a, "-ksp_initial_guess_nonzero")) {
+      flag(&o->initial_guess_nonzero);
+    } else if (!strcmp(a, "-ksp_converged_use_initial_residual_norm")) {
+      flag(&o->converged_use_initial_residual_norm);
+    } else if (!strcmp(a, "-ksp_converged_use_min_initial_residual_norm")) {
+      flag(&o->converged_use_min_initial_residual_norm);
     } else if (!strcmp(a, "-ksp_monitor")) {
       o->monitor = 1;
     } else if (!strcmp(a, "-ksp_converged_reason")) {
       o->converged_reason = 1;
     }
   }
-  return PB_OK;
+  return check_ref_norm_opts(o);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -294,6 +316,7 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
   if (opts) k->opts = *opts;
   else pb_ksp_opts_default(&k->opts);
   if (k->opts.check_every < 1) k->opts.check_every = 8;
+  if (check_ref_norm_opts(&k->opts) != PB_OK) return fail(PB_ERR_ARG);
   // SOR / MG / FFT iterations are expensive and few: poll the device flag more often -- every
   // iteration with the spectral PC (1-3 iterations per solve: an iteration enqueued ahead of the
   // poll costs its skipped launches, ~0.15 ms of a 512^3 config-5 solve, more than the idle
@@ -329,8 +352,9 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
     if (field_alloc(&k->w, vb) != hipSuccess || field_alloc(&k->z, vb) != hipSuccess)
       return fail(set_error(PB_ERR_ALLOC, "KSP work vectors: out of device memory"));
   }
-  // [1]: the folded iteration's second slot
-  if (hipMalloc(&k->d_st, 2 * sizeof(CgState)) != hipSuccess)
+  // [1]: the folded iteration's second slot; behind them two doubles: the sums of M^-1 b a
+  // stored-z setup from a nonzero guess takes for its reference norm (guess_bsums)
+  if (hipMalloc(&k->d_st, 2 * sizeof(CgState) + 2 * sizeof(double)) != hipSuccess)
     return fail(set_error(PB_ERR_ALLOC, "KSP state: out of device memory"));
   *out = k;
   return PB_OK;
@@ -359,6 +383,73 @@ static int pc_apply_dev(pb_ksp* k, const double* r, double* z, const int* skip, 
   *np = 0;
   if (k->fft) return fftpc_apply(k->fft, r, z, skip, k->d_st, np);
   return mg_apply(k->mg, r, z, skip, k->d_st, np);
+}
+
+// Setup from a nonzero initial guess (-ksp_initial_guess_nonzero): r = b - A x0, p = 0, z0 and
+// stage 0 with KSPConvergedDefault's reference norm; x0 is read only
+static int guess_setup(pb_ksp* k, const double* b, const double* x0, double dinv) {
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const int ref = k->opts.converged_use_initial_residual_norm
+                      ? 1
+                      : (k->opts.converged_use_min_initial_residual_norm ? 2 : 0);
+  int np = 0;
+  if (k->stored_z()) {
+    const double* bsums = nullptr;
+    if (ref != 1) {
+      // the reference norm ||N(M^-1 b)||: one more PC application, its sums kept aside
+      PB_TRY(pc_apply_dev(k, b, k->z, nullptr, &np));
+      if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, b, k->d_st, &np));
+      PB_TRY(cg_reduce_allreduce(ctx, ctx->d_partials, np, 4));
+      PB_HIP(hipMemcpyAsync(k->guess_bsums(), ctx->d_scalars, 2 * sizeof(double),
+                            hipMemcpyDeviceToDevice, ctx->stream));
+      bsums = k->guess_bsums();
+    }
+    PB_TRY(op_apply_raw(k->A, x0, k->w));
+    PB_TRY(launch_cg_guess_resid(g, b, k->w, k->r, k->pb[0], dinv, nullptr));
+    PB_TRY(pc_apply_dev(k, k->r, k->z, nullptr, &np));
+    if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, k->r, k->d_st, &np));
+    return cg_finalize_guess(ctx, np, 4, bsums, ref, k->d_st, k->d_hist, k->h_done_dev);
+  }
+  if (!fused_kind(k->A->kind)) {  // compact / assembled A with Jacobi / no PC
+    PB_TRY(op_apply_raw(k->A, x0, k->w));
+    PB_TRY(launch_cg_guess_resid(g, b, k->w, k->r, k->pb[0], dinv, &np));
+    return cg_finalize_guess(ctx, np, 6, nullptr, ref, k->d_st, k->d_hist, k->h_done_dev);
+  }
+  // the fused pass; split grids exchange x0's boundary planes under the interior planes
+  Star s{k->A->cx, k->A->cy, k->A->cz, k->A->cc};
+  StencilPlanes gp;
+  const double* hi = x0 + (g->nzl - 1) * g->plane;
+  if (!ctx->split) {
+    gp.ghost_lo = hi;  // periodic wrap: no copy
+    gp.ghost_hi = x0;
+    PB_TRY(launch_cg_guess_init(g, s, x0, b, k->r, k->pb[0], gp, dinv, PLANES_ALL, 0, &np));
+  } else {
+    gp.ghost_lo = g->ghost_lo;
+    gp.ghost_hi = g->ghost_hi;
+    if (g->nzl < 3) {
+      PB_TRY(halo_exchange(g, x0, hi));
+      PB_TRY(launch_cg_guess_init(g, s, x0, b, k->r, k->pb[0], gp, dinv, PLANES_ALL, 0, &np));
+    } else {
+      int nb1 = 0, nb2 = 0;
+      ScopedTimer tm(ctx, "cg_init_guess");
+      PB_TRY(halo_begin(g, x0, hi));
+      PB_TRY(launch_cg_guess_init(g, s, x0, b, k->r, k->pb[0], gp, dinv, PLANES_INTERIOR, 0,
+                                  &nb1));
+      PB_TRY(halo_end(g));
+      PB_TRY(launch_cg_guess_init(g, s, x0, b, k->r, k->pb[0], gp, dinv, PLANES_BOUNDARY, nb1,
+                                  &nb2));
+      np = nb1 + nb2;
+    }
+  }
+  PB_TRY(cg_finalize_guess(ctx, np, 6, nullptr, ref, k->d_st, k->d_hist, k->h_done_dev));
+  if (k->sr) {
+    // KSPSolve_CG_SingleReduction's setup as from a zero guess: pass S over r0
+    PB_TRY(sr_pass_s(k, k->r, k->d_st, &np, 0));
+    PB_TRY(cg_sr_finalize(ctx, sr_region(ctx, 0), np, k->d_st, k->d_hist, k->h_done_dev, -1,
+                          true));
+  }
+  return PB_OK;
 }
 
 int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
@@ -419,7 +510,13 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   // implicit -- the setup reads b in place of r, and the first iteration writes p = z, x = alpha p
   // and r = b - alpha w without reading them (three vector passes fewer)
   k->lazy0 = k->stored_z() && !fused_kind(k->A->kind) && tune("ksp_lazy0", 1) != 0;
-  if (k->stored_z()) {
+  if (k->opts.initial_guess_nonzero) {
+    // (read on every begin: a reused KSP warm-starts each solve of a time loop from its x)
+    PB_CHECK_ARG(b != x, "a nonzero initial guess needs distinct b and x");
+    PB_TRY(check_ref_norm_opts(&k->opts));
+    k->lazy0 = false;  // x0 is not 0: every update accumulates onto it, none may overwrite
+    PB_TRY(guess_setup(k, b->d, x->d, st.dinv));
+  } else if (k->stored_z()) {
     // r = b, x = 0, p = 0; z = M^-1 r; sums of z (KSPSolve_CG setup, PC_LEFT)
     const size_t vb = (size_t)g->nlocal * sizeof(double);
     const double* r0 = k->lazy0 ? b->d : k->r;

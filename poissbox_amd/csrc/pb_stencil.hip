@@ -284,6 +284,46 @@ struct SrSums {
   }
 };
 
+// CG setup from a nonzero initial guess (-ksp_initial_guess_nonzero) with Jacobi / no PC: the field
+// is x0, the engine's Laplacian y = A x0 (reference order); r = b - y and p = 0 are stored, x0 is
+// left alone. Sums: the setup's four of s = dinv r (s, s^2, s.r, r: cg_init_kernel's) and, from b
+// already in registers, dinv b and (dinv b)^2 -- the stopping reference ||N(M^-1 b)|| of
+// KSPConvergedDefault without a pass of its own. Reads x0, b and writes r, p: 32 B/DoF, pass B's
+// pattern (PST, no x update), whose launch shape it takes.
+struct GuessInit {
+  static constexpr int NS = 6, NE = 1;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true, WIDE8 = true;
+  static constexpr bool PREFETCH = true;
+  double* __restrict__ r;
+  double* __restrict__ p;
+  const double* __restrict__ b;
+  double dinv;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ const double* src(int) const { return b; }
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[1][V], double* acc, int nt) const {
+    double rv[V], zero[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      rv[e] = op[0][e] - w[e];
+      zero[e] = 0.0;
+      const double s = dinv * rv[e];
+      acc[0] += s;
+      acc[1] += s * s;
+      acc[2] += s * rv[e];
+      acc[3] += rv[e];
+      const double sb = dinv * op[0][e];
+      acc[4] += sb;
+      acc[5] += sb * sb;
+    }
+    store_row<V>(r, idx, rv, nt);
+    store_row<V>(p, idx, zero, nt);
+    (void)c;
+  }
+};
 
 // Epi::qop(a) (optional): operand a is raw z-queue array qop(a) of the centre plane (-1: loaded)
 template <class E, class = void>
@@ -1063,6 +1103,82 @@ int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p,
                      dinv, ctx->d_partials);
   PB_HIP(hipGetLastError());
   return cg_reduce_update(ctx, 0, nb, 4, st, hist, h_done, -1);
+}
+
+// Setup from a nonzero initial guess: the fused pass (GuessInit) over the planes of `mode`; its
+// six sums per block go to ctx->d_partials + part_off * 6
+int launch_cg_guess_init(pb_grid* g, const Star& s, const double* x0, const double* b, double* r,
+                         double* p, const StencilPlanes& gp, double dinv, int mode, int part_off,
+                         int* nblocks) {
+  ScopedTimer tm(g->ctx, timer_name(mode, "cg_init_guess", "cg_init_guess_interior",
+                                    "cg_init_guess_boundary"));
+  return launch_any(g, s, PlainLoad{x0}, gp, GuessInit{r, p, b, dinv}, nullptr, mode, part_off,
+                    nblocks);
+}
+
+// cg_finalize_kernel's stage 0 for a setup from a nonzero guess: reduces `width` (4 or 6) sums per
+// block in a fixed order (mode bit 1), then runs stage 0 with the stopping reference `ref`
+// (REF_*; mode bit 2). The sums of dinv b and (dinv b)^2 behind ||N(M^-1 b)|| are sums[4..5]
+// (width 6: the fused pass took them) or bsums[0..1] (taken earlier from M^-1 b)
+__global__ __launch_bounds__(256) void cg_guess_finalize_kernel(const double* __restrict__ parts,
+                                                                int nparts, int width,
+                                                                double* sums, int mode,
+                                                                const double* bsums, int ref,
+                                                                CgState* st, double* hist,
+                                                                int* h_done) {
+  constexpr int W = 6;
+  if (mode & 1) {
+    __shared__ double red[256][W];
+    for (int s = 0; s < width; ++s) {
+      double v = 0.0;
+      for (int b = threadIdx.x; b < nparts; b += 256) v += parts[(int64_t)b * width + s];
+      red[threadIdx.x][s] = v;
+    }
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+      if ((int)threadIdx.x < off)
+        for (int s = 0; s < width; ++s) red[threadIdx.x][s] += red[threadIdx.x + off][s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0)
+      for (int s = 0; s < width; ++s) sums[s] = red[0][s];
+  }
+  if (!(mode & 2) || threadIdx.x != 0) return;
+  double S[kMaxSums];
+  for (int s = 0; s < kMaxSums; ++s) S[s] = s < 4 ? sums[s] : 0.0;
+  double bnorm = 0.0;
+  if (ref != REF_INITIAL) {
+    const double* bs = bsums ? bsums : sums + 4;
+    double zz = bs[1];
+    if (st->nullspace) {
+      const double delta = bs[0] / st->ntot;
+      zz = bs[1] - st->ntot * delta * delta;
+    }
+    bnorm = norm_from_sq(zz);
+  }
+  cg_stage0(*st, S, hist, h_done, ref, bnorm);
+}
+
+int cg_finalize_guess(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
+                      CgState* st, double* hist, int* h_done) {
+  double* sums = ctx->d_scalars;
+  if (!ctx->split) {
+    hipLaunchKernelGGL(cg_guess_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
+                       (const double*)ctx->d_partials, nparts, width, sums, 3, bsums, ref, st, hist,
+                       h_done);
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+  }
+  hipLaunchKernelGGL(cg_guess_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
+                     (const double*)ctx->d_partials, nparts, width, sums, 1, bsums, ref, st, hist,
+                     h_done);
+  PB_HIP(hipGetLastError());
+  PB_TRY(allreduce_device(ctx, sums, width));
+  hipLaunchKernelGGL(cg_guess_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
+                     (const double*)ctx->d_partials, nparts, width, sums, 2, bsums, ref, st, hist,
+                     h_done);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
 }
 
 int launch_cg_boundary(pb_grid* g, const double* r, const double* p_old, CgState* st,

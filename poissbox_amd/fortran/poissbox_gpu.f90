@@ -56,6 +56,9 @@ module poissbox_gpu
      integer(c_int) :: mg_levels, mg_coarse_its
      real(c_double) :: sor_omega
      integer(c_int) :: cg_single_reduction
+     integer(c_int) :: initial_guess_nonzero
+     integer(c_int) :: converged_use_initial_residual_norm
+     integer(c_int) :: converged_use_min_initial_residual_norm
   end type pb_ksp_opts
 
   type, bind(C), public :: pb_ksp_result
