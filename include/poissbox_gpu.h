@@ -174,6 +174,16 @@ int pb_vec_scale(pb_vec* v, double alpha);
 int pb_vec_dot(const pb_vec* x, const pb_vec* y, double* out); /* global sum x.y   */
 int pb_vec_norm2(const pb_vec* v, double* out);              /* global ||v||_2    */
 int pb_vec_sum(const pb_vec* v, double* out);                /* global sum v      */
+/* ≙ VecMDot / VecMAXPY: nv vectors (0 <= nv <= 16, else PB_ERR_ARG; nv = 0 returns at once) of
+ * x's / y's grid (else PB_ERR_ARG) in ONE pass over memory; collective over the ranks.
+ * pb_vec_mdot: out[i] = global sum x . y[i]; y[i] may be x. x and every y[i] are read once
+ * (8 (nv + 1) B/DoF); per-block partial sums reduced in a fixed order, one allreduce of all nv
+ * values, one copy to the host: deterministic run to run.
+ * pb_vec_maxpy: y += sum_i alpha[i] x[i]; no x[i] may be y (PB_ERR_ARG). 8 (nv + 2) B/DoF. Every
+ * element is evaluated in the order ((y + a0 x0) + a1 x1) + ... with every product and every sum
+ * rounded (no FMA contraction), in the vector body and in the tail of an odd length alike. */
+int pb_vec_mdot(const pb_vec* x, int nv, const pb_vec* const* y, double* out);
+int pb_vec_maxpy(pb_vec* y, int nv, const double* alpha, const pb_vec* const* x);
 /* Owned values in natural (i fastest) order of this rank's slab; count = nlocal. */
 int pb_vec_set_values_host(pb_vec* v, const double* owned);
 int pb_vec_get_values_host(const pb_vec* v, double* owned);
@@ -213,6 +223,8 @@ enum pb_ksp_type { PB_KSP_CG = 0 };
  * operator's when P is PB_OP_COMPACT, else the 7-point star's); periodic, power-of-two extents in
  * 64..1024. Not in the reference: the spectrally exact PC for config 5. */
 enum pb_pc_type { PB_PC_NONE = 0, PB_PC_JACOBI = 1, PB_PC_SOR = 2, PB_PC_MG = 3, PB_PC_FFT = 4 };
+/* -ksp_guess_type (PETSc KSPGuess): how pb_ksp_solve forms its initial guess */
+enum pb_guess_type { PB_GUESS_NONE = 0, PB_GUESS_FISCHER = 1 };
 /* PETSc KSPConvergedReason values */
 enum pb_ksp_reason {
   PB_KSP_ITERATING = 0, PB_KSP_CONVERGED_RTOL = 2, PB_KSP_CONVERGED_ATOL = 3,
@@ -255,6 +267,15 @@ typedef struct {
   int converged_use_min_initial_residual_norm; /* -ksp_converged_use_min_initial_residual_norm
                         (KSPConvergedDefaultSetUMIRNorm): min(||N(M^-1 b)||, ||z_0||). Setting
                         both is PB_ERR_ARG, as in PETSc. Neither has an effect without a guess */
+  int guess_type;    /* -ksp_guess_type none|fischer (PETSc KSPGuessFischer, model 1): pb_ksp_solve
+                        projects b onto the span of the last solves' directions for its initial
+                        guess, runs as with initial_guess_nonzero = 1 (whatever that field says; the
+                        x passed in is ignored and overwritten), and adds the solution's new
+                        direction afterwards. The KSP keeps 2 maxl + 1 vectors. Default none */
+  int guess_fischer_model; /* -ksp_guess_fischer_model <model>[,<maxl>]: only model 1 (2 and 3:
+                        PB_ERR_UNSUPPORTED) */
+  int guess_fischer_maxl;  /* stored directions, 1..16 (else PB_ERR_ARG), default 10; when the
+                        space is full the next solve restarts it from its solution alone */
 } pb_ksp_opts;
 typedef struct {
   int reason;
@@ -269,7 +290,8 @@ int pb_ksp_opts_default(pb_ksp_opts* opts);
  * -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
  * -pc_sor_omega, and the PetscOptionsBool flags -ksp_cg_single_reduction,
  * -ksp_initial_guess_nonzero, -ksp_converged_use_initial_residual_norm,
- * -ksp_converged_use_min_initial_residual_norm [true|false]); unknown options are ignored.
+ * -ksp_converged_use_min_initial_residual_norm [true|false]), -ksp_guess_type none|fischer and
+ * -ksp_guess_fischer_model <model>[,<maxl>]; unknown options are ignored.
  * -pc_type sor: one symmetric red-black SOR sweep (PETSc PCSOR default: 1 local symmetric sweep,
  * here in red-black order). -pc_type mg (or gamg): geometric V(1,1) multigrid with red-black SOR
  * smoothing on the 7-point P (README.md:40-45 recommends GAMG + SOR). Both need even extents. */
@@ -296,7 +318,21 @@ int pb_ksp_destroy(pb_ksp* ksp);
 int pb_ksp_pc_apply(pb_ksp* ksp, const pb_vec* r, pb_vec* z);
 /* number of multigrid levels in use (1 for SOR, 0 for Jacobi / none) */
 int pb_ksp_pc_levels(const pb_ksp* ksp, int* levels);
-/* One-shot convenience: ≙ solve(P, A, x, b). */
+/* Projected initial guess (guess_type = PB_GUESS_FISCHER; every call returns PB_ERR_STATE on a
+ * KSP created without it). pb_ksp_solve calls form before and update after the solve by itself;
+ * callers of the split form (pb_ksp_begin with initial_guess_nonzero = 1) call them around it.
+ *   form(b, x):   x = the projection of b's solution onto the stored directions (x as passed in is
+ *                 ignored; 0 while nothing is stored); a copy stays inside the KSP for update.
+ *   update(b, x): after a solve of b from the formed guess: adds the direction x - guess (A-image
+ *                 orthonormalised against the stored ones) unless it is 0 or not finite; a full
+ *                 space restarts from x alone. b is not read (model 1).
+ *   reset:        forget every direction. size: directions stored now / at most. */
+int pb_ksp_guess_form(pb_ksp* ksp, const pb_vec* b, pb_vec* x);
+int pb_ksp_guess_update(pb_ksp* ksp, const pb_vec* b, const pb_vec* x);
+int pb_ksp_guess_reset(pb_ksp* ksp);
+int pb_ksp_guess_size(const pb_ksp* ksp, int* curl, int* maxl);
+/* One-shot convenience: ≙ solve(P, A, x, b). Accepts guess_type too, but its KSP lives for one
+ * solve: no direction is kept, the solve runs from x = 0 as a nonzero guess. */
 int pb_solve(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_vec* b, pb_vec* x,
              pb_ksp_result* res, double* history, int64_t history_cap);
 

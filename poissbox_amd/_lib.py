@@ -31,7 +31,9 @@ class KspOpts(C.Structure):
                 ("mg_levels", C.c_int), ("mg_coarse_its", C.c_int), ("sor_omega", c_d),
                 ("cg_single_reduction", C.c_int), ("initial_guess_nonzero", C.c_int),
                 ("converged_use_initial_residual_norm", C.c_int),
-                ("converged_use_min_initial_residual_norm", C.c_int)]
+                ("converged_use_min_initial_residual_norm", C.c_int),
+                ("guess_type", C.c_int), ("guess_fischer_model", C.c_int),
+                ("guess_fischer_maxl", C.c_int)]
 
 
 class KspResult(C.Structure):
@@ -85,6 +87,8 @@ _SIGS = {
     "pb_vec_aypx": [c_p, c_d, c_p],
     "pb_vec_scale": [c_p, c_d],
     "pb_vec_dot": [c_p, c_p, P_d],
+    "pb_vec_mdot": [c_p, C.c_int, C.POINTER(c_p), P_d],
+    "pb_vec_maxpy": [c_p, C.c_int, P_d, C.POINTER(c_p)],
     "pb_vec_norm2": [c_p, P_d],
     "pb_vec_sum": [c_p, P_d],
     "pb_vec_set_values_host": [c_p, P_d],
@@ -106,6 +110,10 @@ _SIGS = {
     "pb_ksp_iterate": [c_p, c_i64],
     "pb_ksp_end": [c_p, C.POINTER(KspResult), P_d, c_i64],
     "pb_ksp_destroy": [c_p],
+    "pb_ksp_guess_form": [c_p, c_p, c_p],
+    "pb_ksp_guess_update": [c_p, c_p, c_p],
+    "pb_ksp_guess_reset": [c_p],
+    "pb_ksp_guess_size": [c_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pb_ksp_pc_apply": [c_p, c_p, c_p],
     "pb_ksp_pc_levels": [c_p, C.POINTER(C.c_int)],
     "pb_solve": [c_p, c_p, C.POINTER(KspOpts), c_p, c_p, C.POINTER(KspResult), P_d, c_i64],

@@ -280,6 +280,22 @@ class Vec:
         L.call("pb_vec_dot", self.h, y.h, C.byref(out))
         return out.value
 
+    def mdot(self, ys):
+        """VecMDot: numpy array of self . y for the up to 16 vectors ys, in one pass."""
+        out = np.zeros(len(ys))
+        arr = (C.c_void_p * max(len(ys), 1))(*[y.h.value for y in ys])
+        L.call("pb_vec_mdot", self.h, len(ys), arr, _dptr(out))
+        return out
+
+    def maxpy(self, alphas, xs):
+        """VecMAXPY: self += sum_i alphas[i] xs[i] (up to 16 vectors) in one pass."""
+        a = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        if a.size != len(xs):
+            raise ValueError(f"{a.size} coefficients for {len(xs)} vectors")
+        a = np.concatenate([a, [0.0]])  # (a valid pointer also for no vectors)
+        arr = (C.c_void_p * max(len(xs), 1))(*[x.h.value for x in xs])
+        L.call("pb_vec_maxpy", self.h, len(xs), _dptr(a), arr)
+
     def norm(self):
         out = C.c_double()
         L.call("pb_vec_norm2", self.h, C.byref(out))
@@ -390,6 +406,23 @@ class KSP:
         L.call("pb_ksp_end", self.h, C.byref(res), _dptr(hist), hist.size)
         self.result = res
         return res.reason, res.its, hist[: res.nhist].copy()
+
+    def guess_form(self, b, x):
+        """-ksp_guess_type fischer: x = the projected guess for b (solve() does this itself)."""
+        L.call("pb_ksp_guess_form", self.h, b.h, x.h)
+
+    def guess_update(self, b, x):
+        """Add the direction of the solution x of b (solved from the last formed guess)."""
+        L.call("pb_ksp_guess_update", self.h, b.h, x.h)
+
+    def guess_reset(self):
+        L.call("pb_ksp_guess_reset", self.h)
+
+    def guess_size(self):
+        """(directions stored, most that are kept)."""
+        curl, maxl = C.c_int(), C.c_int()
+        L.call("pb_ksp_guess_size", self.h, C.byref(curl), C.byref(maxl))
+        return curl.value, maxl.value
 
     def pc_apply(self, r, z):
         """PCApply: z = M^-1 r (no null-space removal)."""

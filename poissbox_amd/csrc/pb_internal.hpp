@@ -562,6 +562,32 @@ int vec_reduce(pb_ctx* ctx, int kind, const double* x, const double* y, int64_t 
 int copy_probe(pb_ctx* ctx, int64_t n, int reps, std::vector<float>& ms,
                const double* src = nullptr, double* dst = nullptr);
 
+// ---- multi-vector ops and the projected initial guess's passes (pb_guess.hip) ----
+constexpr int kMaxVecs = 16;
+// the vectors of a multi-dot / multi-axpy: travels by value in the kernel arguments
+struct VecTable {
+  const double* p[kMaxVecs];
+};
+// multi-axpy coefficients: host values by value, or sign * dev[i] read from device memory (the
+// sums a multi-dot left there: no host round trip between the two)
+struct MCoef {
+  double host[kMaxVecs];
+  const double* dev = nullptr;
+  double sign = 1.0;
+};
+// d_out[i] = global sum x . y[i], i < nv (1..16): one pass, per-block partials into
+// ctx->d_partials, reduce_partials(width = nv), one allreduce_device; the sums stay on the device
+int launch_mdot(pb_ctx* ctx, const double* x, int nv, const VecTable& y, int64_t n, double* d_out);
+// y = ((y + a0 x0) + a1 x1) + ... (nv in 0..16; from_zero: y is written without being read, the
+// chain starts at 0); y2 != nullptr: the result is stored there too; d_norm2 != nullptr: the
+// global sum of y_new^2 is left there (nv = 0: of y as it is, nothing stored)
+int launch_maxpy(pb_ctx* ctx, double* y, double* y2, int nv, const VecTable& x, const MCoef& c,
+                 int64_t n, bool from_zero, double* d_norm2);
+int launch_guess_diff(pb_ctx* ctx, const double* a, const double* b, double* out, int64_t n);
+// b = s b, xdst = s xsrc in one launch
+int launch_guess_scale(pb_ctx* ctx, double* b, const double* xsrc, double* xdst, double s,
+                       int64_t n);
+
 // ---- grid with an explicit slab (multigrid levels) ----
 int grid_create_part(pb_ctx* ctx, const int64_t n[3], const double L[3], int64_t k0, int64_t nzl,
                      pb_grid** out);

@@ -1065,6 +1065,45 @@ int pb_vec_dot(const pb_vec* x, const pb_vec* y, double* out) {
   return vec_reduce(x->grid->ctx, 1, x->d, y->d, x->nlocal, out);
 }
 
+int pb_vec_mdot(const pb_vec* x, int nv, const pb_vec* const* y, double* out) {
+  PB_CHECK_ARG(x && nv >= 0 && nv <= kMaxVecs, "multi-dot: nv outside 0..16");
+  if (nv == 0) return PB_OK;
+  PB_CHECK_ARG(y && out, "bad multi-dot args");
+  VecTable t;
+  for (int i = 0; i < kMaxVecs; ++i) t.p[i] = nullptr;
+  for (int i = 0; i < nv; ++i) {
+    PB_CHECK_ARG(same_layout(x, y[i]), "vectors of different grids");
+    t.p[i] = y[i]->d;
+  }
+  pb_ctx* ctx = x->grid->ctx;
+  double* dsum = ctx->d_scalars + 8;  // [8, 24): the vector reductions' slots
+  PB_TRY(launch_mdot(ctx, x->d, nv, t, x->nlocal, dsum));
+  PB_HIP(hipMemcpyAsync(ctx->h_scalars, dsum, nv * sizeof(double), hipMemcpyDeviceToHost,
+                        ctx->stream));
+  PB_SYNC(ctx, "multi-dot");
+  for (int i = 0; i < nv; ++i) out[i] = ctx->h_scalars[i];
+  return PB_OK;
+}
+
+int pb_vec_maxpy(pb_vec* y, int nv, const double* alpha, const pb_vec* const* x) {
+  PB_CHECK_ARG(y && nv >= 0 && nv <= kMaxVecs, "multi-axpy: nv outside 0..16");
+  if (nv == 0) return PB_OK;
+  PB_CHECK_ARG(alpha && x, "bad multi-axpy args");
+  VecTable t;
+  MCoef c{};
+  for (int i = 0; i < kMaxVecs; ++i) {
+    t.p[i] = nullptr;
+    c.host[i] = 0.0;
+  }
+  for (int i = 0; i < nv; ++i) {
+    PB_CHECK_ARG(same_layout(y, x[i]), "vectors of different grids");
+    PB_CHECK_ARG(x[i] != y, "multi-axpy: x[i] must not be y");
+    t.p[i] = x[i]->d;
+    c.host[i] = alpha[i];
+  }
+  return launch_maxpy(y->grid->ctx, y->d, nullptr, nv, t, c, y->nlocal, false, nullptr);
+}
+
 int pb_vec_norm2(const pb_vec* v, double* out) {
   PB_CHECK_ARG(v && out, "bad norm args");
   double s = 0.0;

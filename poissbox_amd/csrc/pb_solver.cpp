@@ -67,6 +67,16 @@ struct pb_ksp {
   // partial-sum blocks of the last iteration (folded: reduced by the next pass P's prologue)
   bool sr = false;
   int sr_nparts = 0;
+  // projected initial guess (-ksp_guess_type fischer; PETSc KSPGuessFischer model 1): curl stored
+  // pairs (xt[i], bt[i] = A xt[i]) with the bt orthonormal in the 2-norm, and the last formed
+  // guess. d_coef: [0..15] the multi-dot's sums, [16] the new direction's norm^2
+  struct Fischer {
+    int maxl = 0, curl = 0;
+    std::vector<double*> xt, bt;
+    double* guess = nullptr;
+    double* d_coef = nullptr;
+  };
+  Fischer* fg = nullptr;
 };
 
 static int sr_pass_s(pb_ksp* k, const double* r, const CgState* st, int* nparts, int64_t n);
@@ -217,6 +227,18 @@ int pb_ksp_opts_default(pb_ksp_opts* o) {
   o->initial_guess_nonzero = 0;
   o->converged_use_initial_residual_norm = 0;
   o->converged_use_min_initial_residual_norm = 0;
+  o->guess_type = PB_GUESS_NONE;
+  o->guess_fischer_model = 1;  // PETSc's -ksp_guess_fischer_model default "1,10"
+  o->guess_fischer_maxl = 10;
+  return PB_OK;
+}
+
+static int check_guess_opts(int model, int maxl) {
+  if (model == 2 || model == 3)
+    return set_error(PB_ERR_UNSUPPORTED, "-ksp_guess_fischer_model %d: only model 1", model);
+  if (model != 1) return set_error(PB_ERR_ARG, "-ksp_guess_fischer_model %d: no such model", model);
+  if (maxl < 1 || maxl > kMaxVecs)
+    return set_error(PB_ERR_ARG, "-ksp_guess_fischer_model: maxl %d outside 1..%d", maxl, kMaxVecs);
   return PB_OK;
 }
 
@@ -287,6 +309,20 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
       flag(&o->converged_use_initial_residual_norm);
     } else if (!strcmp(a, "-ksp_converged_use_min_initial_residual_norm")) {
       flag(&o->converged_use_min_initial_residual_norm);
+    } else if (!strcmp(a, "-ksp_guess_type") && v) {
+      if (!strcmp(v, "none")) o->guess_type = PB_GUESS_NONE;
+      else if (!strcmp(v, "fischer")) o->guess_type = PB_GUESS_FISCHER;
+      else return set_error(PB_ERR_UNSUPPORTED, "-ksp_guess_type %s: only none, fischer", v);
+      ++i;
+    } else if (!strcmp(a, "-ksp_guess_fischer_model") && v && v[0] >= '0' && v[0] <= '9') {
+      // <model>[,<maxl>] (PetscOptionsIntArray: a bare model keeps maxl)
+      const int model = atoi(v);
+      const char* comma = strchr(v, ',');
+      const int maxl = comma ? atoi(comma + 1) : o->guess_fischer_maxl;
+      PB_TRY(check_guess_opts(model, maxl));
+      o->guess_fischer_model = model;
+      o->guess_fischer_maxl = maxl;
+      ++i;
     } else if (!strcmp(a, "-ksp_monitor")) {
       o->monitor = 1;
     } else if (!strcmp(a, "-ksp_converged_reason")) {
@@ -356,6 +392,27 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
   // stored-z setup from a nonzero guess takes for its reference norm (guess_bsums)
   if (hipMalloc(&k->d_st, 2 * sizeof(CgState) + 2 * sizeof(double)) != hipSuccess)
     return fail(set_error(PB_ERR_ALLOC, "KSP state: out of device memory"));
+  if (k->opts.guess_type != PB_GUESS_NONE) {
+    if (k->opts.guess_type != PB_GUESS_FISCHER)
+      return fail(set_error(PB_ERR_UNSUPPORTED, "unknown guess_type %d", k->opts.guess_type));
+    const int rc = check_guess_opts(k->opts.guess_fischer_model, k->opts.guess_fischer_maxl);
+    if (rc != PB_OK) return fail(rc);
+    // 2 maxl + 1 fields: xt[maxl], bt[maxl] and the last formed guess
+    pb_ksp::Fischer* f = k->fg = new pb_ksp::Fischer();
+    f->maxl = k->opts.guess_fischer_maxl;
+    f->xt.assign(f->maxl, nullptr);
+    f->bt.assign(f->maxl, nullptr);
+    bool ok = field_alloc(&f->guess, vb) == hipSuccess;
+    for (int i = 0; ok && i < f->maxl; ++i)
+      ok = field_alloc(&f->xt[i], vb) == hipSuccess && field_alloc(&f->bt[i], vb) == hipSuccess;
+    if (!ok)
+      return fail(set_error(PB_ERR_ALLOC, "projected guess: %d vectors: out of device memory",
+                            2 * f->maxl + 1));
+    if (hipMalloc(&f->d_coef, (kMaxVecs + 1) * sizeof(double)) != hipSuccess)
+      return fail(set_error(PB_ERR_ALLOC, "projected guess state: out of device memory"));
+    if (hipMemsetAsync(f->guess, 0, vb, g->ctx->stream) != hipSuccess)
+      return fail(set_error(PB_ERR_HIP, "projected guess: clearing the stored guess failed"));
+  }
   *out = k;
   return PB_OK;
 }
@@ -1031,9 +1088,153 @@ int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
   return PB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Projected initial guess (PETSc KSPGuessFischer, model 1; DESIGN.md "Projected initial guess")
+// ---------------------------------------------------------------------------------------------
+// x = sum_i (b . bt[i]) xt[i], and the same into f->guess: one multi-dot, one two-output
+// multi-axpy onto 0 reading its coefficients from the device (no host round trip)
+static int fischer_form(pb_ksp* k, const double* b, double* x) {
+  pb_ksp::Fischer* f = k->fg;
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const size_t vb = (size_t)g->nlocal * sizeof(double);
+  if (f->curl == 0) {
+    PB_HIP(hipMemsetAsync(x, 0, vb, ctx->stream));
+    PB_HIP(hipMemsetAsync(f->guess, 0, vb, ctx->stream));
+    return PB_OK;
+  }
+  VecTable t;
+  for (int i = 0; i < kMaxVecs; ++i) t.p[i] = i < f->curl ? f->bt[i] : nullptr;
+  PB_TRY(launch_mdot(ctx, b, f->curl, t, g->nlocal, f->d_coef));
+  for (int i = 0; i < f->curl; ++i) t.p[i] = f->xt[i];
+  MCoef c{};
+  c.dev = f->d_coef;
+  c.sign = 1.0;
+  return launch_maxpy(ctx, x, f->guess, f->curl, t, c, g->nlocal, true, nullptr);
+}
+
+// the norm the last pass left in d_coef[16] as its square: the one host read of an update
+static int fischer_norm(pb_ksp* k, double* norm) {
+  pb_ctx* ctx = k->A->grid->ctx;
+  PB_HIP(hipMemcpyAsync(ctx->h_scalars, k->fg->d_coef + kMaxVecs, sizeof(double),
+                        hipMemcpyDeviceToHost, ctx->stream));
+  PB_SYNC(ctx, "projected guess update");
+  *norm = sqrt(ctx->h_scalars[0]);
+  return PB_OK;
+}
+
+static int fischer_matvec(pb_ksp* k, const double* x, double* y) {
+  ScopedTimer tm(k->A->grid->ctx, "guess_matvec");
+  return op_apply_raw(k->A, x, y);
+}
+
+// after a solve from f->guess: the new direction x - guess, its A-image orthonormalised against
+// the stored ones; a direction that is 0 or not finite is not added
+static int fischer_update(pb_ksp* k, const double* x) {
+  pb_ksp::Fischer* f = k->fg;
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const int64_t n = g->nlocal;
+  VecTable t;
+  for (int i = 0; i < kMaxVecs; ++i) t.p[i] = nullptr;
+  MCoef c{};
+  double* nrm2 = f->d_coef + kMaxVecs;
+  double norm = 0.0;
+  if (f->curl == f->maxl) {  // space full: restart from this solution alone
+    PB_TRY(fischer_matvec(k, x, f->bt[0]));
+    PB_TRY(launch_maxpy(ctx, f->bt[0], nullptr, 0, t, c, n, false, nrm2));
+    PB_TRY(fischer_norm(k, &norm));
+    f->curl = 0;
+    if (!std::isfinite(norm) || norm == 0.0) return PB_OK;
+    PB_TRY(launch_guess_scale(ctx, f->bt[0], x, f->xt[0], 1.0 / norm, n));
+    f->curl = 1;
+    return PB_OK;
+  }
+  const int l = f->curl;
+  double* xn = f->xt[l];
+  double* bn = f->bt[l];
+  if (l == 0)
+    PB_HIP(hipMemcpyAsync(xn, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  else
+    PB_TRY(launch_guess_diff(ctx, x, f->guess, xn, n));
+  PB_TRY(fischer_matvec(k, xn, bn));
+  if (l > 0) {
+    // alpha[i] = -(bn . bt[i]); bn += sum alpha[i] bt[i] (its norm^2 in the same pass);
+    // xn += sum alpha[i] xt[i]
+    for (int i = 0; i < l; ++i) t.p[i] = f->bt[i];
+    PB_TRY(launch_mdot(ctx, bn, l, t, n, f->d_coef));
+    c.dev = f->d_coef;
+    c.sign = -1.0;
+    PB_TRY(launch_maxpy(ctx, bn, nullptr, l, t, c, n, false, nrm2));
+    for (int i = 0; i < l; ++i) t.p[i] = f->xt[i];
+    PB_TRY(launch_maxpy(ctx, xn, nullptr, l, t, c, n, false, nullptr));
+  } else {
+    PB_TRY(launch_maxpy(ctx, bn, nullptr, 0, t, c, n, false, nrm2));
+  }
+  PB_TRY(fischer_norm(k, &norm));
+  if (!std::isfinite(norm) || norm == 0.0) return PB_OK;
+  PB_TRY(launch_guess_scale(ctx, bn, xn, xn, 1.0 / norm, n));
+  f->curl = l + 1;
+  return PB_OK;
+}
+
+static int fischer_check(const pb_ksp* k, const pb_vec* b, const pb_vec* x) {
+  PB_CHECK_ARG(k, "ksp is NULL");
+  if (!k->fg) return set_error(PB_ERR_STATE, "KSP created without -ksp_guess_type fischer");
+  PB_CHECK_ARG(b && x && b != x, "the projected guess needs distinct b and x");
+  PB_CHECK_ARG(b->grid == k->A->grid && x->grid == k->A->grid, "vector/operator grid mismatch");
+  return PB_OK;
+}
+
+int pb_ksp_guess_form(pb_ksp* k, const pb_vec* b, pb_vec* x) {
+  PB_TRY(fischer_check(k, b, x));
+  return fischer_form(k, b->d, x->d);
+}
+
+int pb_ksp_guess_update(pb_ksp* k, const pb_vec* b, const pb_vec* x) {
+  PB_TRY(fischer_check(k, b, x));
+  return fischer_update(k, x->d);
+}
+
+int pb_ksp_guess_reset(pb_ksp* k) {
+  PB_CHECK_ARG(k, "ksp is NULL");
+  if (!k->fg) return set_error(PB_ERR_STATE, "KSP created without -ksp_guess_type fischer");
+  k->fg->curl = 0;
+  return PB_OK;
+}
+
+int pb_ksp_guess_size(const pb_ksp* k, int* curl, int* maxl) {
+  PB_CHECK_ARG(k, "ksp is NULL");
+  if (!k->fg) return set_error(PB_ERR_STATE, "KSP created without -ksp_guess_type fischer");
+  if (curl) *curl = k->fg->curl;
+  if (maxl) *maxl = k->fg->maxl;
+  return PB_OK;
+}
+
+// form, the solve exactly as with initial_guess_nonzero = 1 (also while the space is empty and
+// x = 0: PETSc's guess_zero is false once the guess object touched x), update
+static int solve_projected(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res,
+                           double* history, int64_t cap) {
+  PB_TRY(fischer_check(k, b, x));
+  PB_TRY(fischer_form(k, b->d, x->d));
+  const int user_flag = k->opts.initial_guess_nonzero;
+  k->opts.initial_guess_nonzero = 1;
+  const int rc = pb_ksp_begin(k, b, x);
+  k->opts.initial_guess_nonzero = user_flag;
+  PB_TRY(rc);
+  PB_TRY(pb_ksp_iterate(k, k->opts.max_it + 2 * (int64_t)k->opts.check_every));
+  pb_ksp_result r;
+  PB_TRY(pb_ksp_end(k, &r, history, cap));
+  if (res) *res = r;
+  // a non-finite direction must never enter the basis
+  if (r.reason == PB_KSP_DIVERGED_NANORINF) return PB_OK;
+  return fischer_update(k, x->d);
+}
+
 int pb_ksp_solve(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
                  int64_t cap) {
   ScopedTimer tm(k->A->grid->ctx, "KSPSolve");
+  if (k->opts.guess_type != PB_GUESS_NONE) return solve_projected(k, b, x, res, history, cap);
   PB_TRY(pb_ksp_begin(k, b, x));
   PB_TRY(pb_ksp_iterate(k, k->opts.max_it + 2 * (int64_t)k->opts.check_every));
   return pb_ksp_end(k, res, history, cap);
@@ -1049,6 +1250,13 @@ int pb_ksp_destroy(pb_ksp* k) {
   field_free(k->z);
   if (k->mg) mg_destroy(k->mg);
   fftpc_destroy(k->fft);
+  if (k->fg) {
+    for (double* p : k->fg->xt) field_free(p);
+    for (double* p : k->fg->bt) field_free(p);
+    field_free(k->fg->guess);
+    if (k->fg->d_coef) (void)hipFree(k->fg->d_coef);
+    delete k->fg;
+  }
   if (k->d_st) (void)hipFree(k->d_st);
   if (k->d_hist) (void)hipFree(k->d_hist);
   if (k->h_done) (void)hipHostFree(k->h_done);
@@ -1085,6 +1293,14 @@ int pb_ksp_pc_levels(const pb_ksp* k, int* levels) {
 int pb_solve(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_vec* b, pb_vec* x,
              pb_ksp_result* res, double* history, int64_t cap) {
   pb_ksp* k = nullptr;
+  pb_ksp_opts one;
+  if (opts && opts->guess_type == PB_GUESS_FISCHER) {
+    // this KSP lives for one solve and keeps no direction: one pair of vectors is enough
+    PB_TRY(check_guess_opts(opts->guess_fischer_model, opts->guess_fischer_maxl));
+    one = *opts;
+    one.guess_fischer_maxl = 1;
+    opts = &one;
+  }
   PB_TRY(pb_ksp_create(A, P, opts, &k));
   int rc = pb_ksp_solve(k, b, x, res, history, cap);
   pb_ksp_destroy(k);

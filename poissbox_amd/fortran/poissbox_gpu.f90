@@ -59,6 +59,9 @@ module poissbox_gpu
      integer(c_int) :: initial_guess_nonzero
      integer(c_int) :: converged_use_initial_residual_norm
      integer(c_int) :: converged_use_min_initial_residual_norm
+     integer(c_int) :: guess_type            ! -ksp_guess_type none (0) | fischer (1)
+     integer(c_int) :: guess_fischer_model   ! -ksp_guess_fischer_model <model>[,<maxl>]
+     integer(c_int) :: guess_fischer_maxl
   end type pb_ksp_opts
 
   type, bind(C), public :: pb_ksp_result
@@ -379,6 +382,39 @@ module poissbox_gpu
        type(pb_ksp_opts) :: o
        type(pb_ksp_result) :: res
        integer(c_int64_t), value :: cap
+     end function
+     !! ≙ VecMDot / VecMAXPY: y, x are arrays of nv vector handles
+     integer(c_int) function c_pb_vec_mdot(x, nv, y, out) bind(C, name="pb_vec_mdot")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: x
+       integer(c_int), value :: nv
+       type(c_ptr), dimension(*) :: y
+       real(c_double), dimension(*) :: out
+     end function
+     integer(c_int) function c_pb_vec_maxpy(y, nv, alpha, x) bind(C, name="pb_vec_maxpy")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: y
+       integer(c_int), value :: nv
+       real(c_double), dimension(*) :: alpha
+       type(c_ptr), dimension(*) :: x
+     end function
+     !! projected initial guess of a KSP handle created with guess_type = 1 (fischer)
+     integer(c_int) function c_pb_ksp_guess_form(ksp, b, x) bind(C, name="pb_ksp_guess_form")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp, b, x
+     end function
+     integer(c_int) function c_pb_ksp_guess_update(ksp, b, x) bind(C, name="pb_ksp_guess_update")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp, b, x
+     end function
+     integer(c_int) function c_pb_ksp_guess_reset(ksp) bind(C, name="pb_ksp_guess_reset")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp
+     end function
+     integer(c_int) function c_pb_ksp_guess_size(ksp, curl, maxl) bind(C, name="pb_ksp_guess_size")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp
+       integer(c_int) :: curl, maxl
      end function
   end interface
 
