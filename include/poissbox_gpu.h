@@ -218,7 +218,25 @@ int pb_op_get_ownership_range(const pb_op* op, int64_t* first, int64_t* next);
 int pb_vec_get_ownership_range(const pb_vec* v, int64_t* first, int64_t* next);
 
 /* ---- KSP (replaces solve(P, A, x, b), src/poissbox.f90:269-298 -> KSPSolve) ---- */
-enum pb_ksp_type { PB_KSP_CG = 0 };
+/* -ksp_type (src/poissbox.f90:269-298: solve hands its KSP to KSPSetFromOptions, so the type is the
+ * caller's choice; the reference README puts richardson on the multigrid levels).
+ *  PB_KSP_PREONLY (PETSc KSPSolve_PREONLY): x = N(M^-1 b), one PC application and the constant
+ *    null-space removal KSP adds (nullspace = 1). its = 1, reason PB_KSP_CONVERGED_ITS, rnorm =
+ *    rnorm0 = 0, nhist = 0: no norm, no reduction, no NaN check. b and x must be distinct
+ *    (PB_ERR_ARG). With PB_PC_FFT the mean subtraction is skipped: P^+ zeroes mode 0 itself, the
+ *    result's mean is at rounding level (|mean| / max|x| = 1.2e-19 on the CPU oracle at 32x40x48),
+ *    and subtracting it would add a 24 B/DoF pass (sum, then subtract) to a 5-pass solve. With
+ *    -pc_type fft this is the direct solve of P's symbol. initial_guess_nonzero or a guess_type is
+ *    PB_ERR_ARG at pb_ksp_create (PETSc: "preonly doesn't make sense with nonzero initial guess;
+ *    you probably want richardson"); pb_ksp_begin / iterate / end return PB_ERR_UNSUPPORTED.
+ *  PB_KSP_RICHARDSON (PETSc KSPSolve_Richardson, PC_LEFT, preconditioned norm, default test):
+ *    x += richardson_scale N(M^-1 (b - A x)); iteration i logs ||z_i||, tests it with its = i,
+ *    and updates if the test gives nothing; after max_it updates one more norm is logged and
+ *    tested before PB_KSP_DIVERGED_ITS: nhist = its + 1 always. b and x must be distinct
+ *    (PB_ERR_ARG: b is read by every update). Works with every operator, PC,
+ *    initial_guess_nonzero, guess_type fischer and the split form, as PB_KSP_CG does.
+ * cg_single_reduction is a CG option: the other two types ignore it. */
+enum pb_ksp_type { PB_KSP_CG = 0, PB_KSP_PREONLY = 1, PB_KSP_RICHARDSON = 2 };
 /* PB_PC_FFT (-pc_type fft): z = P^+ r by separable Hartley transforms with P's symbol (the compact
  * operator's when P is PB_OP_COMPACT, else the 7-point star's); periodic, power-of-two extents in
  * 64..1024. Not in the reference: the spectrally exact PC for config 5. */
@@ -237,7 +255,7 @@ typedef struct {
   double atol;       /* -ksp_atol   (1e-50)               */
   double dtol;       /* -ksp_divtol (1e5)                 */
   int64_t max_it;    /* -ksp_max_it (10000)               */
-  int ksp_type;      /* -ksp_type cg                      */
+  int ksp_type;      /* -ksp_type cg|preonly|richardson   */
   int pc_type;       /* -pc_type none|jacobi|sor|mg       */
   int nullspace;     /* constant null space (src/poissbox.f90:285-291), default 1 */
   int monitor;       /* -ksp_monitor: print ||z_k|| per iteration after the solve (rank 0) */
@@ -276,6 +294,9 @@ typedef struct {
                         PB_ERR_UNSUPPORTED) */
   int guess_fischer_maxl;  /* stored directions, 1..16 (else PB_ERR_ARG), default 10; when the
                         space is full the next solve restarts it from its solution alone */
+  double richardson_scale; /* -ksp_richardson_scale (PETSc KSPRichardsonSetScale), default 1.0;
+                        must be finite (PB_ERR_ARG). -ksp_richardson_self_scale is parsed and
+                        PB_ERR_UNSUPPORTED */
 } pb_ksp_opts;
 typedef struct {
   int reason;
@@ -286,8 +307,8 @@ typedef struct {
                         after a breakdown exit (beta = 0, indefinite PC / matrix) */
 } pb_ksp_result;
 int pb_ksp_opts_default(pb_ksp_opts* opts);
-/* Parses PETSc-style options (-ksp_type, -pc_type, -ksp_rtol, -ksp_atol, -ksp_divtol,
- * -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
+/* Parses PETSc-style options (-ksp_type cg|preonly|richardson, -ksp_richardson_scale, -pc_type,
+ * -ksp_rtol, -ksp_atol, -ksp_divtol, -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
  * -pc_sor_omega, and the PetscOptionsBool flags -ksp_cg_single_reduction,
  * -ksp_initial_guess_nonzero, -ksp_converged_use_initial_residual_norm,
  * -ksp_converged_use_min_initial_residual_norm [true|false]), -ksp_guess_type none|fischer and

@@ -33,7 +33,7 @@ class KspOpts(C.Structure):
                 ("converged_use_initial_residual_norm", C.c_int),
                 ("converged_use_min_initial_residual_norm", C.c_int),
                 ("guess_type", C.c_int), ("guess_fischer_model", C.c_int),
-                ("guess_fischer_maxl", C.c_int)]
+                ("guess_fischer_maxl", C.c_int), ("richardson_scale", c_d)]
 
 
 class KspResult(C.Structure):

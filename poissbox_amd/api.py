@@ -22,6 +22,9 @@ from . import _lib as L
 
 STAR7, COMPACT, ASSEMBLED27 = 0, 1, 2
 PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
+# -ksp_type: preonly = one PC application (with -pc_type fft the direct solve), richardson =
+# x += scale M^-1 (b - A x) (ksp_options(richardson_scale=...) or -ksp_richardson_scale)
+KSP_CG, KSP_PREONLY, KSP_RICHARDSON = 0, 1, 2
 
 REASONS = {0: "CONVERGED_ITERATING", 2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL",
            4: "CONVERGED_ITS", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",

@@ -598,6 +598,33 @@ int launch_cg_pc_xr(pb_grid* g, const double* p, const double* w, double* x, con
 int launch_cg_pc_sums(pb_grid* g, const double* z, const double* r, CgState* st, int* nparts);
 int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done);
 
+// ---- stationary solves: -ksp_type richardson / preonly (pb_ksp_stationary.hip, and the engine
+// pass launch_rich_update in pb_stencil.hip) ----
+// Richardson keeps CG's device-resident state (CgState: mu = the mean of the current M^-1 r,
+// it = its = updates done, dp, rnorm0, ttol, reason, done, nlog), history buffer and done flags.
+int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double* q,
+                       const double* b, double* x_out, double* r_out, const StencilPlanes& gp,
+                       const CgState* st, double scale, bool sums, bool skip, int* nparts);
+// x_out = x + scale (dinv q - mean): RichLoad's expression, every product and sum rounded
+int launch_rich_x(pb_grid* g, const double* x, const double* q, double* x_out, const CgState* st,
+                  double scale);
+// r = b - w (w = A x from the operator); nparts != nullptr: the two sums of dinv r - mean
+int launch_rich_resid(pb_grid* g, const double* b, const double* w, double* r, const CgState* st,
+                      bool skip, int* nparts);
+// the two sums of dinv q - mean (setup: q = b or the stored z)
+int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts);
+// `width` sums per block (only t, t^2 are read) of ctx->d_partials reduced and allreduced into
+// ctx->d_scalars; dst != nullptr: the first two copied there (the reference norm's sums of M^-1 b)
+int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst);
+// the norm, history entry, KSPConvergedDefault test and iteration limit after the setup
+// (host_iter = -1; ref = REF_*, bsums as cg_finalize_guess) or after update host_iter
+int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
+                  double* hist, int* h_done, int64_t host_iter);
+// preonly: dst = dinv src (dst == nullptr: src as it is) with its sum per block; x -= sum / ntot
+// from the reduced sum in ctx->d_scalars[0]
+int launch_pre_scale_sum(pb_grid* g, const double* src, double* dst, double dinv, int* nparts);
+int launch_pre_shift(pb_grid* g, double* x, double ntot);
+
 // ---- geometric multigrid / red-black SOR preconditioner (pb_mg.hip) ----
 struct Mg;
 // levels_req: 0 = automatic; pc_type PB_PC_SOR (one symmetric red-black sweep) or PB_PC_MG

@@ -1,0 +1,283 @@
+// pb_ksp_stationary.hip -- the vector kernels and the one-block finalize of the stationary solves:
+// -ksp_type richardson (PETSc KSPSolve_Richardson: x += scale N(M^-1 (b - A x)), PC_LEFT, the
+// preconditioned norm, KSPConvergedDefault) and -ksp_type preonly (KSPSolve_PREONLY: x = N(M^-1 b)).
+// The hot step of Richardson on the 7-point operator is one stencil-engine pass (RichLoad /
+// RichEpi, pb_stencil.hip); the kernels here are its unfused form, the steps around operators
+// without an engine (compact, assembled, split grids) and the scalar logic. The device-resident
+// state, done flag, history and polling are CG's (CgState, pb_solver.cpp).
+#include "pb_cg_device.hpp"
+
+namespace pb {
+
+// ---------------------------------------------------------------------------------------------
+// Scalar logic: iteration i has z_i = N(M^-1 r_i) behind the sums S = (sum t, sum t^2) of
+// t = M^-1 r_i - mean_old (shifted by the previous mean, as CG's stage 2: the sums stay accurate
+// when the residual is almost constant). setup: i = 0 and the stopping reference; else i = it + 1
+// (the update before this norm happened: every kernel of it ran, the state was not done).
+//   ||z_i|| -> NaN / Inf: DIVERGED_NANORINF, its = i; history[i]; the default test with its = i;
+//   no reason and i = max_it: DIVERGED_ITS; else the mean for the next update.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void rich_stage(CgState& st, const double* S, bool setup, int ref,
+                                           double bnorm, double* hist, int* h_done,
+                                           int64_t host_iter) {
+  if (setup) {
+    st.it = 0;
+    st.its = 0;
+    st.reason = 0;
+    st.done = 0;
+    st.mu = 0.0;
+    st.nlog = 0;
+    st.pend_iter = -1;
+    st.pend_count = 0;
+  }
+  if (!st.done) {
+    const int64_t i = setup ? 0 : st.it + 1;
+    const double N = st.ntot;
+    double delta = 0.0, zz = S[1];
+    if (st.nullspace) {
+      delta = S[0] / N;
+      zz = S[1] - N * delta * delta;
+    }
+    const double dp = norm_from_sq(zz);
+    st.it = i;
+    st.its = i;
+    st.dp = dp;
+    if (setup) {
+      double rn0 = dp;  // REF_ZERO_GUESS, REF_INITIAL
+      if (ref == REF_RHS) rn0 = bnorm == 0.0 ? dp : bnorm;
+      else if (ref == REF_MIN) rn0 = fmin(bnorm, dp);
+      st.rnorm0 = rn0;
+      st.ttol = fmax(st.rtol * rn0, st.atol);
+    }
+    if (i < st.nhist) {
+      hist[i] = dp;
+      st.nlog = i + 1;
+    }
+    if (!finite(dp)) {
+      st.reason = PB_KSP_DIVERGED_NANORINF;
+      st.done = 1;
+    } else if (dp <= st.ttol) {
+      st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
+      st.done = 1;
+    } else if (!(setup && ref == REF_ZERO_GUESS) && dp >= st.dtol * st.rnorm0) {
+      // (from a zero guess ||z_0|| is the reference itself: no test at i = 0, as CG's stage 0)
+      st.reason = PB_KSP_DIVERGED_DTOL;
+      st.done = 1;
+    } else if (i >= st.max_it) {
+      st.reason = PB_KSP_DIVERGED_ITS;
+      st.done = 1;
+    } else {
+      st.mu = st.mu + delta;
+    }
+  }
+  h_done[setup ? 0 : host_iter + 1] = st.done;
+}
+
+// mode bit 1: reduce nparts x width partials into sums[0..1] in a fixed order (only the first two
+// sums of a block are read: CG's 4-wide PC sums carry t, t^2 first); bit 2: rich_stage from
+// sums[] (split around the allreduce on several ranks). bsums / ref: cg_guess_finalize_kernel's.
+__global__ __launch_bounds__(256) void rich_finalize_kernel(const double* __restrict__ parts,
+                                                            int nparts, int width, double* sums,
+                                                            int mode, const double* bsums, int ref,
+                                                            CgState* st, double* hist, int* h_done,
+                                                            int64_t host_iter) {
+  if (mode & 1) {
+    __shared__ double red[256][2];
+    for (int s = 0; s < 2; ++s) {
+      double v = 0.0;
+      for (int b = threadIdx.x; b < nparts; b += 256) v += parts[(int64_t)b * width + s];
+      red[threadIdx.x][s] = v;
+    }
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+      if ((int)threadIdx.x < off)
+        for (int s = 0; s < 2; ++s) red[threadIdx.x][s] += red[threadIdx.x + off][s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      sums[0] = red[0][0];
+      sums[1] = red[0][1];
+    }
+  }
+  if (!(mode & 2) || threadIdx.x != 0) return;
+  const double S[2] = {sums[0], sums[1]};
+  const bool setup = host_iter < 0;
+  double bnorm = 0.0;
+  if (setup && (ref == REF_RHS || ref == REF_MIN)) {
+    double zz = bsums[1];
+    if (st->nullspace) {
+      const double delta = bsums[0] / st->ntot;
+      zz = bsums[1] - st->ntot * delta * delta;
+    }
+    bnorm = norm_from_sq(zz);
+  }
+  rich_stage(*st, S, setup, ref, bnorm, hist, h_done, host_iter);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Vector kernels. Those of an iteration exit at entry once the state is done (enqueued ahead of
+// the host's poll): x and r then stay as the last update left them.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rich_x_kernel(const double* __restrict__ x,
+                                                     const double* __restrict__ q,
+                                                     double* __restrict__ x_out, int64_t n,
+                                                     const CgState* st, double scale) {
+  if (st->done) return;
+  const double dinv = st->dinv, shift = -st->mu;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double z = dinv * q[i];
+    z = z + shift;
+    const double u = scale * z;
+    x_out[i] = x[i] + u;
+  }
+}
+
+template <bool SUMS>
+__global__ __launch_bounds__(256) void rich_resid_kernel(const double* __restrict__ b,
+                                                         const double* __restrict__ w,
+                                                         double* __restrict__ r, int64_t n,
+                                                         double* parts, const CgState* st,
+                                                         int skip) {
+  if (skip && st->done) return;
+  const double dinv = st->dinv, mu = st->mu;
+  double acc[2] = {0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double rv = b[i] - w[i];
+    r[i] = rv;
+    if constexpr (SUMS) {
+      const double t = dinv * rv - mu;
+      acc[0] += t;
+      acc[1] += t * t;
+    }
+  }
+  if constexpr (SUMS) block_partials<2>(acc, parts);
+}
+
+__global__ __launch_bounds__(256) void rich_sums_kernel(const double* __restrict__ q, int64_t n,
+                                                        double* parts, const CgState* st) {
+  const double dinv = st->dinv, mu = st->mu;
+  double acc[2] = {0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double t = dinv * q[i] - mu;
+    acc[0] += t;
+    acc[1] += t * t;
+  }
+  block_partials<2>(acc, parts);
+}
+
+// preonly: dst = dinv src (PCApply_Jacobi / PCApply_None) and the sum of it, or the sum alone
+__global__ __launch_bounds__(256) void pre_scale_sum_kernel(const double* __restrict__ src,
+                                                            double* __restrict__ dst, int64_t n,
+                                                            double dinv, double* parts) {
+  double acc[2] = {0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double v = src[i];
+    if (dst) {
+      v = dinv * v;
+      dst[i] = v;
+    }
+    acc[0] += v;
+  }
+  block_partials<2>(acc, parts);
+}
+
+// MatNullSpaceRemove of the constant: x -= sum / ntot
+__global__ __launch_bounds__(256) void pre_shift_kernel(double* __restrict__ x, int64_t n,
+                                                        const double* sums, double ntot) {
+  const double mean = sums[0] / ntot;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    x[i] = x[i] - mean;
+}
+
+static int vec_blocks(pb_ctx* ctx, int64_t n) {
+  const int64_t b = (n + 255) / 256, cap = (int64_t)ctx->num_cus * 8;
+  return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
+int launch_rich_x(pb_grid* g, const double* x, const double* q, double* x_out, const CgState* st,
+                  double scale) {
+  ScopedTimer tm(g->ctx, "rich_axpy");
+  hipLaunchKernelGGL(rich_x_kernel, dim3(vec_blocks(g->ctx, g->nlocal)), dim3(256), 0,
+                     g->ctx->stream, x, q, x_out, g->nlocal, st, scale);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+int launch_rich_resid(pb_grid* g, const double* b, const double* w, double* r, const CgState* st,
+                      bool skip, int* nparts) {
+  ScopedTimer tm(g->ctx, "rich_resid_vec");
+  const int nb = vec_blocks(g->ctx, g->nlocal);
+  if (nparts) {
+    hipLaunchKernelGGL(rich_resid_kernel<true>, dim3(nb), dim3(256), 0, g->ctx->stream, b, w, r,
+                       g->nlocal, g->ctx->d_partials, st, skip ? 1 : 0);
+    *nparts = nb;
+  } else {
+    hipLaunchKernelGGL(rich_resid_kernel<false>, dim3(nb), dim3(256), 0, g->ctx->stream, b, w, r,
+                       g->nlocal, g->ctx->d_partials, st, skip ? 1 : 0);
+  }
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts) {
+  const int nb = vec_blocks(g->ctx, g->nlocal);
+  hipLaunchKernelGGL(rich_sums_kernel, dim3(nb), dim3(256), 0, g->ctx->stream, q, g->nlocal,
+                     g->ctx->d_partials, st);
+  PB_HIP(hipGetLastError());
+  *nparts = nb;
+  return PB_OK;
+}
+
+int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst) {
+  hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
+                     (const double*)ctx->d_partials, nparts, width, ctx->d_scalars, 1,
+                     (const double*)nullptr, 0, (CgState*)nullptr, (double*)nullptr,
+                     (int*)nullptr, (int64_t)0);
+  PB_HIP(hipGetLastError());
+  if (ctx->split) PB_TRY(allreduce_device(ctx, ctx->d_scalars, 2));
+  if (dst)
+    PB_HIP(hipMemcpyAsync(dst, ctx->d_scalars, 2 * sizeof(double), hipMemcpyDeviceToDevice,
+                          ctx->stream));
+  return PB_OK;
+}
+
+int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
+                  double* hist, int* h_done, int64_t host_iter) {
+  const double* parts = ctx->d_partials;
+  if (!ctx->split) {
+    hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
+                       width, ctx->d_scalars, 3, bsums, ref, st, hist, h_done, host_iter);
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+  }
+  PB_TRY(rich_reduce(ctx, nparts, width, nullptr));
+  hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
+                     width, ctx->d_scalars, 2, bsums, ref, st, hist, h_done, host_iter);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+int launch_pre_scale_sum(pb_grid* g, const double* src, double* dst, double dinv, int* nparts) {
+  ScopedTimer tm(g->ctx, "preonly_sum");
+  const int nb = vec_blocks(g->ctx, g->nlocal);
+  hipLaunchKernelGGL(pre_scale_sum_kernel, dim3(nb), dim3(256), 0, g->ctx->stream, src, dst,
+                     g->nlocal, dinv, g->ctx->d_partials);
+  PB_HIP(hipGetLastError());
+  *nparts = nb;
+  return PB_OK;
+}
+
+int launch_pre_shift(pb_grid* g, double* x, double ntot) {
+  ScopedTimer tm(g->ctx, "preonly_shift");
+  hipLaunchKernelGGL(pre_shift_kernel, dim3(vec_blocks(g->ctx, g->nlocal)), dim3(256), 0,
+                     g->ctx->stream, x, g->nlocal, (const double*)g->ctx->d_scalars, ntot);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+}  // namespace pb

@@ -40,6 +40,18 @@ struct pb_ksp {
   double* pb[4] = {nullptr, nullptr, nullptr, nullptr};
   double* w = nullptr;   // generic (unfused) path only
   double* z = nullptr;   // generic path only
+  // Richardson (-ksp_type richardson): update i reads xbuf(i) and writes xbuf(i + 1) -- the
+  // engine pass forms x_new at a point's neighbours from x_old there, so x is never updated in
+  // place; the caller's x is xbuf(even), and pb_ksp_end copies x2 back after an odd number of
+  // updates (the device's count: launches that exited at entry flipped nothing). Jacobi / none:
+  // r ping-pongs likewise (rich_rbuf), r_0 = b read in place from a zero guess
+  double* x2 = nullptr;
+  bool rich_guess = false;  // this solve started from a nonzero guess (r_0 is in r, not b)
+  bool rich() const { return opts.ksp_type == PB_KSP_RICHARDSON; }
+  double* xbuf(int64_t i) const { return (i & 1) ? x2 : x->d; }
+  const double* rich_rbuf(int64_t i) const {
+    return i == 0 && !rich_guess ? b->d : ((i & 1) ? r2 : r);
+  }
   pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
   int fold_nparts_b = 0;     // partial-sum blocks of the last folded pass B
@@ -230,6 +242,7 @@ int pb_ksp_opts_default(pb_ksp_opts* o) {
   o->guess_type = PB_GUESS_NONE;
   o->guess_fischer_model = 1;  // PETSc's -ksp_guess_fischer_model default "1,10"
   o->guess_fischer_maxl = 10;
+  o->richardson_scale = 1.0;  // KSPRichardsonSetScale's default
   return PB_OK;
 }
 
@@ -269,9 +282,21 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
       }
     };
     if (!strcmp(a, "-ksp_type") && v) {
-      if (strcmp(v, "cg")) return set_error(PB_ERR_UNSUPPORTED, "-ksp_type %s: only cg", v);
-      o->ksp_type = PB_KSP_CG;
+      if (!strcmp(v, "cg")) o->ksp_type = PB_KSP_CG;
+      else if (!strcmp(v, "preonly")) o->ksp_type = PB_KSP_PREONLY;
+      else if (!strcmp(v, "richardson")) o->ksp_type = PB_KSP_RICHARDSON;
+      else
+        return set_error(PB_ERR_UNSUPPORTED, "-ksp_type %s: only cg, preonly, richardson", v);
       ++i;
+    } else if (!strcmp(a, "-ksp_richardson_scale") && v) {
+      o->richardson_scale = atof(v);
+      if (!std::isfinite(o->richardson_scale))
+        return set_error(PB_ERR_ARG, "-ksp_richardson_scale %s: not finite", v);
+      ++i;
+    } else if (!strcmp(a, "-ksp_richardson_self_scale")) {
+      int self_scale = 0;
+      flag(&self_scale);
+      if (self_scale) return set_error(PB_ERR_UNSUPPORTED, "-ksp_richardson_self_scale");
     } else if (!strcmp(a, "-pc_type") && v) {
       if (!strcmp(v, "none")) o->pc_type = PB_PC_NONE;
       else if (!strcmp(v, "jacobi")) o->pc_type = PB_PC_JACOBI;
@@ -353,6 +378,16 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
   else pb_ksp_opts_default(&k->opts);
   if (k->opts.check_every < 1) k->opts.check_every = 8;
   if (check_ref_norm_opts(&k->opts) != PB_OK) return fail(PB_ERR_ARG);
+  const int kt = k->opts.ksp_type;
+  if (kt != PB_KSP_CG && kt != PB_KSP_PREONLY && kt != PB_KSP_RICHARDSON)
+    return fail(set_error(PB_ERR_UNSUPPORTED, "unknown ksp_type %d", kt));
+  if (!std::isfinite(k->opts.richardson_scale))
+    return fail(set_error(PB_ERR_ARG, "richardson_scale is not finite"));
+  if (kt == PB_KSP_PREONLY &&
+      (k->opts.initial_guess_nonzero || k->opts.guess_type != PB_GUESS_NONE))
+    return fail(set_error(PB_ERR_ARG,
+                          "preonly doesn't make sense with a nonzero initial guess; you probably "
+                          "want richardson"));
   // SOR / MG / FFT iterations are expensive and few: poll the device flag more often -- every
   // iteration with the spectral PC (1-3 iterations per solve: an iteration enqueued ahead of the
   // poll costs its skipped launches, ~0.15 ms of a 512^3 config-5 solve, more than the idle
@@ -509,8 +544,165 @@ static int guess_setup(pb_ksp* k, const double* b, const double* x0, double dinv
   return PB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Stationary solves: -ksp_type richardson, -ksp_type preonly
+// ---------------------------------------------------------------------------------------------
+// the 7-point operator on one rank: the engine pass reads the periodic wrap planes in place
+static bool rich_engine(const pb_ksp* k) {
+  return fused_kind(k->A->kind) && !k->A->grid->ctx->split;
+}
+
+// r_out = b - A x (+ the sums of dinv r_out - mean with Jacobi / no PC: *np blocks, else 0)
+static int rich_residual(pb_ksp* k, const double* x, double* r_out, bool skip, int* np) {
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const bool sums = !k->stored_z();
+  *np = 0;
+  if (rich_engine(k)) {
+    Star s{k->A->cx, k->A->cy, k->A->cz, k->A->cc};
+    StencilPlanes gp;
+    gp.ghost_lo = gp.ghost_hi = nullptr;
+    gp.wrap = true;
+    return launch_rich_update(g, s, x, nullptr, k->b->d, nullptr, r_out, gp, k->d_st, 0.0, sums,
+                              skip, np);
+  }
+  {
+    OpApplySkip guard(ctx, skip ? &k->d_st->done : nullptr);
+    PB_TRY(op_apply_raw(k->A, x, k->w));
+  }
+  return launch_rich_resid(g, k->b->d, k->w, r_out, k->d_st, skip, sums ? np : nullptr);
+}
+
+// z = M^-1 r of a stored-z PC with the sums of z - mean (4 wide: the PC's own, or CG's sum kernel)
+static int rich_pc(pb_ksp* k, const double* r, const int* skip, int* np) {
+  PB_TRY(pc_apply_dev(k, r, k->z, skip, np));
+  if (*np == 0) PB_TRY(launch_cg_pc_sums(k->A->grid, k->z, r, k->d_st, np));
+  return PB_OK;
+}
+
+// KSPSolve_Richardson's setup: r_0 = b (read in place), x_0 = 0, or r_0 = b - A x_0 from a nonzero
+// guess with CG's reference-norm rules; z_0, its norm, history[0] and the first test
+static int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const size_t vb = (size_t)g->nlocal * sizeof(double);
+  // b is read by every update (r = b - A x) while x is written
+  PB_CHECK_ARG(b != x, "richardson needs distinct b and x");
+  k->sr = false;
+  k->pst = false;
+  k->lazy0 = false;
+  k->defer_x = 0;
+  if (!k->x2 && field_alloc(&k->x2, vb) != hipSuccess)
+    return set_error(PB_ERR_ALLOC, "Richardson solution buffer: out of device memory");
+  if (!k->stored_z() && !k->r2 && field_alloc(&k->r2, vb) != hipSuccess)
+    return set_error(PB_ERR_ALLOC, "Richardson residual buffer: out of device memory");
+  if (!rich_engine(k) && !k->w && field_alloc(&k->w, vb) != hipSuccess)
+    return set_error(PB_ERR_ALLOC, "Richardson work vector: out of device memory");
+  k->b = b;
+  k->x = x;
+  k->rich_guess = k->opts.initial_guess_nonzero != 0;
+  const int width = k->stored_z() ? 4 : 2;
+  int np = 0;
+  if (!k->rich_guess) {
+    PB_HIP(hipMemsetAsync(x->d, 0, vb, ctx->stream));
+    if (k->stored_z()) PB_TRY(rich_pc(k, b->d, nullptr, &np));
+    else PB_TRY(launch_rich_sums(g, b->d, k->d_st, &np));
+    return rich_finalize(ctx, np, width, nullptr, 3, k->d_st, k->d_hist, k->h_done_dev, -1);
+  }
+  PB_TRY(check_ref_norm_opts(&k->opts));
+  const int ref = k->opts.converged_use_initial_residual_norm
+                      ? 1
+                      : (k->opts.converged_use_min_initial_residual_norm ? 2 : 0);
+  const double* bsums = nullptr;
+  if (ref != 1) {  // the reference norm ||N(M^-1 b)||: the sums of M^-1 b kept aside
+    if (k->stored_z()) PB_TRY(rich_pc(k, b->d, nullptr, &np));
+    else PB_TRY(launch_rich_sums(g, b->d, k->d_st, &np));
+    PB_TRY(rich_reduce(ctx, np, width, k->guess_bsums()));
+    bsums = k->guess_bsums();
+  }
+  PB_TRY(rich_residual(k, x->d, k->r, false, &np));
+  if (k->stored_z()) PB_TRY(rich_pc(k, k->r, nullptr, &np));
+  return rich_finalize(ctx, np, width, bsums, ref, k->d_st, k->d_hist, k->h_done_dev, -1);
+}
+
+// one update: x_new = x + scale (M^-1 r - mean), r_new = b - A x_new, z_new and its sums, the
+// norm and the test. On the 7-point operator (one rank) the first two are one engine pass
+// (tuning rich_fused = 0: a vector kernel and the engine's residual pass, bit-identical)
+static int enqueue_rich_iteration(pb_ksp* k) {
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const int64_t i = k->host_iter;
+  const double* xin = k->xbuf(i);
+  double* xout = k->xbuf(i + 1);
+  const double* q = k->stored_z() ? k->z : k->rich_rbuf(i);
+  double* r_out = k->stored_z() ? k->r : (((i + 1) & 1) ? k->r2 : k->r);
+  const double scale = k->opts.richardson_scale;
+  int np = 0;
+  if (rich_engine(k) && tune("rich_fused", 1) != 0) {
+    Star s{k->A->cx, k->A->cy, k->A->cz, k->A->cc};
+    StencilPlanes gp;
+    gp.ghost_lo = gp.ghost_hi = nullptr;
+    gp.wrap = true;
+    PB_TRY(launch_rich_update(g, s, xin, q, k->b->d, xout, r_out, gp, k->d_st, scale,
+                              !k->stored_z(), true, &np));
+  } else {
+    PB_TRY(launch_rich_x(g, xin, q, xout, k->d_st, scale));
+    PB_TRY(rich_residual(k, xout, r_out, true, &np));
+  }
+  if (k->stored_z()) PB_TRY(rich_pc(k, r_out, &k->d_st->done, &np));
+  return rich_finalize(ctx, np, k->stored_z() ? 4 : 2, nullptr, 0, k->d_st, k->d_hist,
+                       k->h_done_dev, i);
+}
+
+// KSPSolve_PREONLY: x = N(M^-1 b). No norm, no reduction but the mean's, no NaN check. The
+// spectral PC zeroes mode 0 itself: its result keeps its rounding-level mean (poissbox_gpu.h)
+static int solve_preonly(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res) {
+  PB_CHECK_ARG(k && b && x, "bad solve args");
+  pb_grid* g = k->A->grid;
+  PB_CHECK_ARG(b->grid == g && x->grid == g, "vector/operator grid mismatch");
+  PB_CHECK_ARG(b != x, "preonly needs distinct b and x");
+  pb_ctx* ctx = g->ctx;
+  int np = 0;
+  if (k->fft) {
+    PB_TRY(fftpc_apply(k->fft, b->d, x->d));
+  } else {
+    if (k->mg) {
+      PB_TRY(mg_apply(k->mg, b->d, x->d));
+      if (k->opts.nullspace) PB_TRY(launch_pre_scale_sum(g, x->d, nullptr, 1.0, &np));
+    } else {
+      const double dinv = k->opts.pc_type == PB_PC_JACOBI ? 1.0 / k->P->cc : 1.0;
+      PB_TRY(launch_pre_scale_sum(g, b->d, x->d, dinv, &np));
+    }
+    if (k->opts.nullspace) {
+      PB_TRY(rich_reduce(ctx, np, 2, nullptr));
+      PB_TRY(launch_pre_shift(g, x->d, (double)(g->n[0] * g->n[1] * g->n[2])));
+    }
+  }
+  PB_SYNC(ctx, "pb_ksp_solve (preonly)");
+  if (res) {
+    res->reason = PB_KSP_CONVERGED_ITS;
+    res->its = 1;
+    res->rnorm = 0.0;
+    res->rnorm0 = 0.0;
+    res->nhist = 0;
+  }
+  if (ctx->rank == 0 && k->opts.converged_reason) {
+    printf("Linear solve converged due to CONVERGED_ITS iterations 1\n");
+    fflush(stdout);
+  }
+  return PB_OK;
+}
+
+static int preonly_split_form(const pb_ksp* k) {
+  if (k && k->opts.ksp_type == PB_KSP_PREONLY)
+    return set_error(PB_ERR_UNSUPPORTED,
+                     "-ksp_type preonly has no split form: use pb_ksp_solve or pb_solve");
+  return PB_OK;
+}
+
 int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   PB_CHECK_ARG(k && b && x, "bad begin args");
+  PB_TRY(preonly_split_form(k));
   pb_grid* g = k->A->grid;
   PB_CHECK_ARG(b->grid == g && x->grid == g, "vector/operator grid mismatch");
   pb_ctx* ctx = g->ctx;
@@ -536,6 +728,15 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   // with SOR / MG the sums are taken over z = M^-1 r itself (dinv = 1)
   st.dinv = k->opts.pc_type == PB_PC_JACOBI ? 1.0 / k->P->cc : 1.0;
   st.ntot = (double)(g->n[0] * g->n[1] * g->n[2]);
+  if (k->rich()) {
+    PB_HIP(hipMemcpyAsync(k->d_st, &st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    PB_TRY(rich_begin(k, b, x));
+    PB_SYNC(ctx, "pb_ksp_begin");
+    k->host_iter = 0;
+    k->stopped = k->h_done[0] != 0;
+    k->begun = true;
+    return PB_OK;
+  }
   // depth 4 (default): 58 instead of 60 B/DoF per iteration, measured 3 % faster at 512^3
   // (profiles/r01/ab_defer_x.txt); the x update sums four alpha p terms instead of adding them
   // one per iteration (rounding-level difference in x only: the history is unaffected)
@@ -964,6 +1165,7 @@ static int enqueue_iteration(pb_ksp* k, bool fold, bool fold_a) {
 
 int pb_ksp_iterate(pb_ksp* k, int64_t iters) {
   PB_CHECK_ARG(k, "ksp is NULL");
+  PB_TRY(preonly_split_form(k));
   if (!k->begun) return set_error(PB_ERR_STATE, "pb_ksp_iterate before pb_ksp_begin");
   pb_ctx* ctx = k->A->grid->ctx;
   const int C = k->opts.check_every;
@@ -978,10 +1180,12 @@ int pb_ksp_iterate(pb_ksp* k, int64_t iters) {
   PB_TRY(ensure_done_cap(k, k->host_iter + iters + 2));
   // one rank, Jacobi, fused operator: the finalize steps ride in the passes' prologues
   // (PB_CG_FOLD=0 keeps the separate finalize launches)
-  const bool fold = C >= 2 && fused_kind(k->A->kind) && !k->stored_z() && tune("cg_fold", 1) != 0;
+  const bool fold = C >= 2 && !k->rich() && fused_kind(k->A->kind) && !k->stored_z() &&
+                    tune("cg_fold", 1) != 0;
   int64_t n = 0;
   for (; n < iters && !k->stopped; ++n) {
-    if (k->sr) PB_TRY(enqueue_sr_iteration(k, fold, n));
+    if (k->rich()) PB_TRY(enqueue_rich_iteration(k));
+    else if (k->sr) PB_TRY(enqueue_sr_iteration(k, fold, n));
     else PB_TRY(enqueue_iteration(k, fold, fold && n > 0));
     const int64_t hi = k->host_iter++;
     // only the iterations the poll below waits for get an event (j = 0 mod C; folded j + 1): an
@@ -1039,6 +1243,7 @@ static const char* reason_name(int r) {
 
 int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
   PB_CHECK_ARG(k, "ksp is NULL");
+  PB_TRY(preonly_split_form(k));
   if (!k->begun) return set_error(PB_ERR_STATE, "pb_ksp_end before pb_ksp_begin");
   pb_ctx* ctx = k->A->grid->ctx;
   PB_SYNC(ctx, "pb_ksp_end");
@@ -1048,7 +1253,12 @@ int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
   CgState st;
   PB_HIP(hipMemcpyAsync(&st, k->d_st, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
   PB_SYNC(ctx, "pb_ksp_end");
-  if (st.pend_iter >= 0) {  // apply the still-deferred alpha_m p_m (p_m lives in pb[(m+1) % ns])
+  if (k->rich() && (st.its & 1)) {  // an odd number of updates: the result is in the other buffer
+    PB_HIP(hipMemcpyAsync(k->x->d, k->x2, (size_t)k->A->grid->nlocal * sizeof(double),
+                          hipMemcpyDeviceToDevice, ctx->stream));
+    PB_SYNC(ctx, "pb_ksp_end");
+  }
+  if (!k->rich() && st.pend_iter >= 0) {  // apply the still-deferred alpha_m p_m (p_m lives in pb[(m+1) % ns])
     const int ns = k->pslots();
     for (int64_t m = 0; m < st.pend_count; ++m)
       PB_TRY(launch_cg_flush(k->A->grid, k->x->d, k->pb[(st.pend_iter + m + 1) % ns], st.pa[m]));
@@ -1233,7 +1443,9 @@ static int solve_projected(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result*
 
 int pb_ksp_solve(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
                  int64_t cap) {
+  PB_CHECK_ARG(k, "ksp is NULL");
   ScopedTimer tm(k->A->grid->ctx, "KSPSolve");
+  if (k->opts.ksp_type == PB_KSP_PREONLY) return solve_preonly(k, b, x, res);
   if (k->opts.guess_type != PB_GUESS_NONE) return solve_projected(k, b, x, res, history, cap);
   PB_TRY(pb_ksp_begin(k, b, x));
   PB_TRY(pb_ksp_iterate(k, k->opts.max_it + 2 * (int64_t)k->opts.check_every));
@@ -1248,6 +1460,7 @@ int pb_ksp_destroy(pb_ksp* k) {
   for (double* p : k->pb) field_free(p);
   field_free(k->w);
   field_free(k->z);
+  field_free(k->x2);
   if (k->mg) mg_destroy(k->mg);
   fftpc_destroy(k->fft);
   if (k->fg) {

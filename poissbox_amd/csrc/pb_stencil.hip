@@ -325,6 +325,78 @@ struct GuessInit {
   }
 };
 
+// Richardson (-ksp_type richardson, PETSc KSPSolve_Richardson) on the 7-point operator: the update
+// and the residual in one pass. The field is x_new = x + scale (dinv q + shift), formed on load
+// from two raw arrays (q = r with Jacobi / no PC, the stored z = M^-1 r otherwise; shift = -mean,
+// the null-space removal), every product and sum rounded (no FMA contraction: the build's
+// -ffp-contract=off), so a vector kernel with the same expression gives the same bits
+// (rich_x_kernel, pb_ksp_stationary.hip). The epilogue stores the centre value x_new and
+// r_new = b - A x_new (reference summation order) and, with SUMS (Jacobi / no PC), takes the sums
+// of t = dinv r_new - mean_old (t, t^2) behind the next iteration's norm and mean. x and (SUMS) r
+// go to other buffers than they are read from: neighbouring waves and blocks still read x_old and
+// q at this point's neighbours while this block stores. Reads x, q, b and writes x, r: 40 B/DoF,
+// pass B's pattern (two streams written, non-temporal), whose launch shape it takes.
+// STOREX = false with PlainLoad: the unfused form's second step, r = b - A x of a stored x, with
+// the same tiles, chunks and partial sums (tuning rich_fused = 0; bit-identical).
+struct RichLoad {
+  static constexpr int NR = 2;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ x;
+  const double* __restrict__ q;
+  const CgState* st;
+  double scale;
+  double dinv = 1.0, shift = 0.0;
+  __device__ __forceinline__ void prepare() {
+    dinv = st->dinv;
+    shift = -st->mu;
+  }
+  __device__ __forceinline__ const double* src(int a) const { return a == 0 ? x : q; }
+  __device__ __forceinline__ double value(const double* raw) const {
+    double z = dinv * raw[1];
+    z = z + shift;
+    const double u = scale * z;
+    return raw[0] + u;
+  }
+};
+template <bool STOREX, bool SUMS>
+struct RichEpi {
+  static constexpr int NS = SUMS ? 2 : 0, NE = 1;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true, WIDE8 = true;
+  static constexpr bool PREFETCH = true;
+  double* __restrict__ x_out;
+  double* __restrict__ r_out;
+  const double* __restrict__ b;
+  const CgState* st;
+  double dinv = 1.0, mu = 0.0;
+  __device__ __forceinline__ void prepare() {
+    if constexpr (SUMS) {
+      dinv = st->dinv;
+      mu = st->mu;
+    }
+  }
+  __device__ __forceinline__ const double* src(int) const { return b; }
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[1][V], double* acc, int nt) const {
+    double rv[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      rv[e] = op[0][e] - w[e];
+      if constexpr (SUMS) {
+        const double s = dinv * rv[e];
+        const double t = s - mu;
+        acc[0] += t;
+        acc[1] += t * t;
+      }
+    }
+    (void)acc;
+    store_row<V>(r_out, idx, rv, nt);
+    if constexpr (STOREX) store_row<V>(x_out, idx, c, nt);
+  }
+};
+
 // Epi::qop(a) (optional): operand a is raw z-queue array qop(a) of the centre plane (-1: loaded)
 template <class E, class = void>
 struct HasQop {
@@ -1114,6 +1186,30 @@ int launch_cg_guess_init(pb_grid* g, const Star& s, const double* x0, const doub
                                     "cg_init_guess_boundary"));
   return launch_any(g, s, PlainLoad{x0}, gp, GuessInit{r, p, b, dinv}, nullptr, mode, part_off,
                     nblocks);
+}
+
+// Richardson's update + residual pass (RichLoad / RichEpi), whole grid, wrap planes or ghosts of
+// x as gp says. q != nullptr: fused, x_out = x + scale (dinv q - mean), r_out = b - A x_out;
+// q == nullptr: r_out = b - A x of the stored x (the unfused form and the nonzero-guess setup).
+// sums: the two sums of dinv r_out - mean per block into ctx->d_partials (*nparts blocks).
+// skip = false: the setup's launch (the state's done flag is not valid yet)
+int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double* q,
+                       const double* b, double* x_out, double* r_out, const StencilPlanes& gp,
+                       const CgState* st, double scale, bool sums, bool skip, int* nparts) {
+  ScopedTimer tm(g->ctx, q ? "rich_update" : "rich_resid");
+  const int* sk = skip ? &st->done : nullptr;
+  *nparts = 0;
+  if (q) {
+    const RichLoad ld{x, q, st, scale};
+    if (sums)
+      return launch_any(g, s, ld, gp, RichEpi<true, true>{x_out, r_out, b, st}, sk, PLANES_ALL, 0,
+                        nparts);
+    return launch_any(g, s, ld, gp, RichEpi<true, false>{x_out, r_out, b, st}, sk);
+  }
+  if (sums)
+    return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, true>{nullptr, r_out, b, st}, sk,
+                      PLANES_ALL, 0, nparts);
+  return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, false>{nullptr, r_out, b, st}, sk);
 }
 
 // cg_finalize_kernel's stage 0 for a setup from a nonzero guess: reduces `width` (4 or 6) sums per

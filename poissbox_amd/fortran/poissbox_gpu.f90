@@ -62,6 +62,7 @@ module poissbox_gpu
      integer(c_int) :: guess_type            ! -ksp_guess_type none (0) | fischer (1)
      integer(c_int) :: guess_fischer_model   ! -ksp_guess_fischer_model <model>[,<maxl>]
      integer(c_int) :: guess_fischer_maxl
+     real(c_double) :: richardson_scale      ! -ksp_richardson_scale (default 1.0)
   end type pb_ksp_opts
 
   type, bind(C), public :: pb_ksp_result
