@@ -235,8 +235,27 @@ int pb_vec_get_ownership_range(const pb_vec* v, int64_t* first, int64_t* next);
  *    tested before PB_KSP_DIVERGED_ITS: nhist = its + 1 always. b and x must be distinct
  *    (PB_ERR_ARG: b is read by every update). Works with every operator, PC,
  *    initial_guess_nonzero, guess_type fischer and the split form, as PB_KSP_CG does.
- * cg_single_reduction is a CG option: the other two types ignore it. */
-enum pb_ksp_type { PB_KSP_CG = 0, PB_KSP_PREONLY = 1, PB_KSP_RICHARDSON = 2 };
+ *  PB_KSP_CHEBYSHEV (PETSc KSPSolve_Chebyshev, PC_LEFT, preconditioned norm, default test): the
+ *    accelerated stationary iteration for a spectrum of M^-1 A inside [emin, emax] -- no inner
+ *    product but the norm's. With scale = 2 / (emax + emin), alpha = 1 - scale emin,
+ *    mu = 1 / alpha, omegaprod = 2 / alpha: iteration i logs ||z_i||, z_i = N(M^-1 (b - A y_i)), and tests it with
+ *    its = i exactly as PB_KSP_RICHARDSON does (nhist = its + 1 always); update 0 is Richardson's
+ *    with richardson_scale = scale, y_1 = y_0 + scale z_0; update i >= 1 is
+ *    y_(i+1) = omega_i ((y_i - y_(i-1)) + scale z_i) + y_(i-1), omega_i = omegaprod rho_i,
+ *    rho_i = 1 / (2 mu - rho_(i-1)), rho_0 = 1 / mu. rho_i is PETSc's c_i / c_(i+1): its recurrence
+ *    c_(k+1) = 2 mu c_k - c_(k-1) overflows in long runs, the ratio does not.
+ *    Bounds: pb_ksp_chebyshev_opts emin / emax, both negative with -pc_type none (A is the Laplacian,
+ *    negative semi-definite; Jacobi's diagonal is negative too, so M^-1 A is positive with it).
+ *    Left at 0, 0 they are estimated once per operator pair (pb_ksp_chebyshev_get_eigenvalues).
+ *    b and x must be distinct (PB_ERR_ARG). Works with every operator, PC, initial_guess_nonzero,
+ *    guess_type fischer and the split form, as PB_KSP_RICHARDSON does; every solve and every
+ *    pb_ksp_begin restarts rho.
+ * cg_single_reduction is a CG option: the other types ignore it. */
+enum pb_ksp_type {
+  PB_KSP_CG = 0, PB_KSP_PREONLY = 1, PB_KSP_RICHARDSON = 2, PB_KSP_CHEBYSHEV = 3
+};
+/* seed of the noise vector (pb_vec_set_random) the Chebyshev eigenvalue estimate starts from */
+#define PB_CHEBYSHEV_ESTEIG_SEED 20240607ULL
 /* PB_PC_FFT (-pc_type fft): z = P^+ r by separable Hartley transforms with P's symbol (the compact
  * operator's when P is PB_OP_COMPACT, else the 7-point star's); periodic, power-of-two extents in
  * 64..1024. Not in the reference: the spectrally exact PC for config 5. */
@@ -255,7 +274,7 @@ typedef struct {
   double atol;       /* -ksp_atol   (1e-50)               */
   double dtol;       /* -ksp_divtol (1e5)                 */
   int64_t max_it;    /* -ksp_max_it (10000)               */
-  int ksp_type;      /* -ksp_type cg|preonly|richardson   */
+  int ksp_type;      /* -ksp_type cg|preonly|richardson|chebyshev */
   int pc_type;       /* -pc_type none|jacobi|sor|mg       */
   int nullspace;     /* constant null space (src/poissbox.f90:285-291), default 1 */
   int monitor;       /* -ksp_monitor: print ||z_k|| per iteration after the solve (rank 0) */
@@ -298,6 +317,18 @@ typedef struct {
                         must be finite (PB_ERR_ARG). -ksp_richardson_self_scale is parsed and
                         PB_ERR_UNSUPPORTED */
 } pb_ksp_opts;
+/* The settings of PB_KSP_CHEBYSHEV (PETSc KSPChebyshevSetEigenvalues, KSPChebyshevEstEigSet).
+ * They have a struct of their own, set on the KSP after pb_ksp_create (pb_ksp_chebyshev_set_opts),
+ * because the layout of pb_ksp_opts is pinned: a KSP that was given none runs with the defaults. */
+typedef struct {
+  double emin, emax; /* -ksp_chebyshev_eigenvalues emin,emax: finite, non-zero, of one sign,
+                        emax > emin (else PB_ERR_ARG); 0, 0 (default): estimate them */
+  double esteig[4];  /* -ksp_chebyshev_esteig a,b,c,d (0, 0.1, 0, 1.1): emin = a min + b max,
+                        emax = c min + d max of the estimated extremes; finite */
+  int esteig_steps;  /* -ksp_chebyshev_esteig_steps: Lanczos steps of the estimate, 1..64 (else
+                        PB_ERR_ARG), default 10. -ksp_chebyshev_esteig_noisy false is
+                        PB_ERR_UNSUPPORTED: the estimate always starts from noise */
+} pb_ksp_chebyshev_opts;
 typedef struct {
   int reason;
   int64_t its;
@@ -307,12 +338,15 @@ typedef struct {
                         after a breakdown exit (beta = 0, indefinite PC / matrix) */
 } pb_ksp_result;
 int pb_ksp_opts_default(pb_ksp_opts* opts);
-/* Parses PETSc-style options (-ksp_type cg|preonly|richardson, -ksp_richardson_scale, -pc_type,
+/* Parses PETSc-style options (-ksp_type cg|preonly|richardson|chebyshev, -ksp_richardson_scale,
+ * -pc_type,
  * -ksp_rtol, -ksp_atol, -ksp_divtol, -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
  * -pc_sor_omega, and the PetscOptionsBool flags -ksp_cg_single_reduction,
  * -ksp_initial_guess_nonzero, -ksp_converged_use_initial_residual_norm,
  * -ksp_converged_use_min_initial_residual_norm [true|false]), -ksp_guess_type none|fischer and
- * -ksp_guess_fischer_model <model>[,<maxl>]; unknown options are ignored.
+ * -ksp_guess_fischer_model <model>[,<maxl>]; unknown options are ignored. The -ksp_chebyshev_*
+ * options are checked here as pb_ksp_chebyshev_opts_parse checks them (the same errors), but
+ * their values are kept by that call only.
  * -pc_type sor: one symmetric red-black SOR sweep (PETSc PCSOR default: 1 local symmetric sweep,
  * here in red-black order). -pc_type mg (or gamg): geometric V(1,1) multigrid with red-black SOR
  * smoothing on the 7-point P (README.md:40-45 recommends GAMG + SOR). Both need even extents. */
@@ -334,6 +368,37 @@ int pb_ksp_begin(pb_ksp* ksp, const pb_vec* b, pb_vec* x);
 int pb_ksp_iterate(pb_ksp* ksp, int64_t iters);
 int pb_ksp_end(pb_ksp* ksp, pb_ksp_result* res, double* history, int64_t history_cap);
 int pb_ksp_destroy(pb_ksp* ksp);
+/* -ksp_chebyshev_eigenvalues emin,emax, -ksp_chebyshev_esteig a,b,c,d,
+ * -ksp_chebyshev_esteig_steps n, -ksp_chebyshev_esteig_noisy [bool] from the same argument list
+ * as pb_ksp_opts_parse; other options are ignored. */
+int pb_ksp_chebyshev_opts_default(pb_ksp_chebyshev_opts* opts);
+int pb_ksp_chebyshev_opts_parse(pb_ksp_chebyshev_opts* opts, int argc, const char* const* argv);
+/* Sets them on a PB_KSP_CHEBYSHEV KSP (PB_ERR_STATE on another type, PB_ERR_ARG for invalid
+ * values, which leave the KSP as it was); an estimate made before is forgotten. */
+int pb_ksp_chebyshev_set_opts(pb_ksp* ksp, const pb_ksp_chebyshev_opts* opts);
+/* pb_solve with these settings (cheb may be NULL: the defaults) */
+int pb_solve_chebyshev(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
+                       const pb_ksp_chebyshev_opts* cheb, const pb_vec* b, pb_vec* x,
+                       pb_ksp_result* res, double* history, int64_t history_cap);
+/* The bounds the next PB_KSP_CHEBYSHEV solve uses (PB_ERR_STATE on a KSP of another type);
+ * *estimated = 0 for the caller's own. Without given bounds this runs the estimate if it has not
+ * run for the operators' current deltas (so it is collective over the ranks):
+ * esteig_steps steps of preconditioned CG-Lanczos on A and the PC, from r_0 = N(v),
+ * v = pb_vec_set_random with
+ * PB_CHEBYSHEV_ESTEIG_SEED (decomposition independent); the Lanczos tridiagonal (diagonal
+ * 1 / alpha_j + beta_(j-1) / alpha_(j-1), off-diagonal sqrt(beta_j) / alpha_j) gives the extremes
+ * through pb_tridiag_extreme_eigenvalues, esteig transforms them. It stops early on a
+ * beta that is 0, negative or not finite, and once r'z has fallen below 1e-24 of its first value
+ * (-pc_type fft with A = P: one step is all there is). PETSc's default estimator is GMRES in the
+ * Euclidean inner product; this is its -esteig_ksp_type cg counterpart. Transformed bounds that
+ * are no valid pair (-pc_type none with the default transform: the spectrum is negative) return
+ * PB_ERR_ARG, here and from the solve; the KSP stays usable. */
+int pb_ksp_chebyshev_get_eigenvalues(pb_ksp* ksp, double* emin, double* emax, int* estimated);
+/* Smallest and largest eigenvalue of the symmetric tridiagonal matrix with diagonal diag[0..n-1]
+ * and off-diagonal off[0..n-2] (off may be NULL when n = 1), by bisection on Sturm counts. Pure
+ * host code, 1 <= n <= 64 and finite entries (else PB_ERR_ARG). */
+int pb_tridiag_extreme_eigenvalues(int n, const double* diag, const double* off, double* lo,
+                                   double* hi);
 /* PCApply(KSPGetPC(ksp), r, z): z = M^-1 r of the configured preconditioner (Jacobi: D^-1 r;
  * SOR / MG: from a zero initial guess), without the null-space removal KSP adds. */
 int pb_ksp_pc_apply(pb_ksp* ksp, const pb_vec* r, pb_vec* z);

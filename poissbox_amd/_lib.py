@@ -36,6 +36,10 @@ class KspOpts(C.Structure):
                 ("guess_fischer_maxl", C.c_int), ("richardson_scale", c_d)]
 
 
+class KspChebyshevOpts(C.Structure):
+    _fields_ = [("emin", c_d), ("emax", c_d), ("esteig", c_d * 4), ("esteig_steps", C.c_int)]
+
+
 class KspResult(C.Structure):
     _fields_ = [("reason", C.c_int), ("its", c_i64), ("rnorm", c_d), ("rnorm0", c_d),
                 ("nhist", c_i64)]
@@ -114,6 +118,14 @@ _SIGS = {
     "pb_ksp_guess_update": [c_p, c_p, c_p],
     "pb_ksp_guess_reset": [c_p],
     "pb_ksp_guess_size": [c_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "pb_ksp_chebyshev_opts_default": [C.POINTER(KspChebyshevOpts)],
+    "pb_ksp_chebyshev_opts_parse": [C.POINTER(KspChebyshevOpts), C.c_int,
+                                    C.POINTER(C.c_char_p)],
+    "pb_ksp_chebyshev_set_opts": [c_p, C.POINTER(KspChebyshevOpts)],
+    "pb_solve_chebyshev": [c_p, c_p, C.POINTER(KspOpts), C.POINTER(KspChebyshevOpts), c_p, c_p,
+                           C.POINTER(KspResult), P_d, c_i64],
+    "pb_ksp_chebyshev_get_eigenvalues": [c_p, P_d, P_d, C.POINTER(C.c_int)],
+    "pb_tridiag_extreme_eigenvalues": [C.c_int, P_d, P_d, P_d, P_d],
     "pb_ksp_pc_apply": [c_p, c_p, c_p],
     "pb_ksp_pc_levels": [c_p, C.POINTER(C.c_int)],
     "pb_solve": [c_p, c_p, C.POINTER(KspOpts), c_p, c_p, C.POINTER(KspResult), P_d, c_i64],

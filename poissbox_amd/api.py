@@ -24,7 +24,9 @@ STAR7, COMPACT, ASSEMBLED27 = 0, 1, 2
 PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
 # -ksp_type: preonly = one PC application (with -pc_type fft the direct solve), richardson =
 # x += scale M^-1 (b - A x) (ksp_options(richardson_scale=...) or -ksp_richardson_scale)
-KSP_CG, KSP_PREONLY, KSP_RICHARDSON = 0, 1, 2
+# chebyshev = the accelerated stationary iteration for a spectrum of M^-1 A in [emin, emax]
+# (-ksp_chebyshev_eigenvalues emin,emax; estimated when not given: KSP.chebyshev_eigenvalues())
+KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV = 0, 1, 2, 3
 
 REASONS = {0: "CONVERGED_ITERATING", 2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL",
            4: "CONVERGED_ITS", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",
@@ -358,6 +360,10 @@ class Mat:
         L.call("pb_op_get_diagonal", self.h, C.byref(d))
         return d.value
 
+    def set_deltas(self, deltas):
+        """(Re)set the spacings the coefficients are built from (assemble_laplacian)."""
+        L.call("pb_op_set_deltas", self.h, _d_3(deltas))
+
     def destroy(self):
         if self.h:
             L.call("pb_op_destroy", self.h)
@@ -368,15 +374,56 @@ def MatMult(A, x, y):
     A.mult(x, y)
 
 
+class KspOptions(L.KspOpts):
+    """pb_ksp_opts (the same layout: no field added) together with the Chebyshev settings, which
+    the C interface keeps in a struct of their own (pb_ksp_chebyshev_opts; `.chebyshev`); KSP()
+    sets them after pb_ksp_create. chebyshev_emin / _emax / _esteig / _esteig_steps read and write
+    that struct."""
+
+    def _cheb(self):
+        if "chebyshev" not in self.__dict__:
+            c = L.KspChebyshevOpts()
+            L.call("pb_ksp_chebyshev_opts_default", C.byref(c))
+            self.__dict__["chebyshev"] = c
+        return self.__dict__["chebyshev"]
+
+    chebyshev = property(_cheb)
+    chebyshev_emin = property(lambda s: s._cheb().emin, lambda s, v: setattr(s._cheb(), "emin", v))
+    chebyshev_emax = property(lambda s: s._cheb().emax, lambda s, v: setattr(s._cheb(), "emax", v))
+    chebyshev_esteig_steps = property(lambda s: s._cheb().esteig_steps,
+                                      lambda s, v: setattr(s._cheb(), "esteig_steps", v))
+
+    @property
+    def chebyshev_esteig(self):
+        return self._cheb().esteig
+
+    @chebyshev_esteig.setter
+    def chebyshev_esteig(self, v):
+        self._cheb().esteig = (C.c_double * 4)(*v)
+
+
 def ksp_options(argv=(), **kw):
-    o = L.KspOpts()
+    o = KspOptions()
     L.call("pb_ksp_opts_default", C.byref(o))
     if argv:
         arr = (C.c_char_p * len(argv))(*[str(a).encode() for a in argv])
         L.call("pb_ksp_opts_parse", C.byref(o), len(argv), arr)
+        L.call("pb_ksp_chebyshev_opts_parse", C.byref(o.chebyshev), len(argv), arr)
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def tridiag_extreme_eigenvalues(diag, off=()):
+    """(smallest, largest) eigenvalue of the symmetric tridiagonal matrix (host code, n <= 64)."""
+    d = np.ascontiguousarray(diag, dtype=np.float64)
+    e = np.ascontiguousarray(off if len(off) else [0.0], dtype=np.float64)
+    if len(off) != max(d.size - 1, 0):
+        raise ValueError("off-diagonal must have n - 1 entries")
+    lo, hi = C.c_double(), C.c_double()
+    L.call("pb_tridiag_extreme_eigenvalues", int(d.size), _dptr(d), _dptr(e), C.byref(lo),
+           C.byref(hi))
+    return lo.value, hi.value
 
 
 class KSP:
@@ -387,6 +434,12 @@ class KSP:
         h = C.c_void_p()
         L.call("pb_ksp_create", A.h, (P or A).h, C.byref(self.opts), C.byref(h))
         self.h = h
+        if self.opts.ksp_type == KSP_CHEBYSHEV and isinstance(self.opts, KspOptions):
+            try:
+                L.call("pb_ksp_chebyshev_set_opts", h, C.byref(self.opts.chebyshev))
+            except L.PbError:
+                self.destroy()
+                raise
 
     def solve(self, b, x):
         """Returns (reason, its, history): the res.nhist logged norms (its + 1 of them, its
@@ -426,6 +479,13 @@ class KSP:
         curl, maxl = C.c_int(), C.c_int()
         L.call("pb_ksp_guess_size", self.h, C.byref(curl), C.byref(maxl))
         return curl.value, maxl.value
+
+    def chebyshev_eigenvalues(self):
+        """(emin, emax, estimated) of the next -ksp_type chebyshev solve; runs the estimate if the
+        bounds were not given and it has not run yet (collective)."""
+        lo, hi, est = C.c_double(), C.c_double(), C.c_int()
+        L.call("pb_ksp_chebyshev_get_eigenvalues", self.h, C.byref(lo), C.byref(hi), C.byref(est))
+        return lo.value, hi.value, bool(est.value)
 
     def pc_apply(self, r, z):
         """PCApply: z = M^-1 r (no null-space removal)."""

@@ -618,8 +618,23 @@ int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts
 int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst);
 // the norm, history entry, KSPConvergedDefault test and iteration limit after the setup
 // (host_iter = -1; ref = REF_*, bsums as cg_finalize_guess) or after update host_iter
+// cheb_mu != 0 (-ksp_type chebyshev): a test that gives nothing also advances the ratio
+// recurrence for the update that follows: st->beta = rho_i = 1 / (2 mu - rho_(i-1)) (rho_0 =
+// 1 / mu), st->alpha = omega_i = omegaprod rho_i -- CG's two fields, unused by these solves
 int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
-                  double* hist, int* h_done, int64_t host_iter);
+                  double* hist, int* h_done, int64_t host_iter, double cheb_mu = 0.0,
+                  double cheb_omegaprod = 0.0);
+// Chebyshev's update i >= 1 (pb_stencil.hip ChebLoad): y_out = omega ((y - ym1) + scale (dinv q -
+// mean)) + ym1 with omega = st->alpha, r_out = b - A y_out, one rank, wrap planes; sums as
+// launch_rich_update's. Update 0 is launch_rich_update with Chebyshev's scale
+int launch_cheb_update(pb_grid* g, const Star& s, const double* y, const double* ym1,
+                       const double* q, const double* b, double* y_out, double* r_out,
+                       const StencilPlanes& gp, const CgState* st, double scale, bool sums,
+                       int* nparts);
+// the same expression as a vector kernel (the unfused form: split grids, compact / assembled
+// operators, tuning cheb_fused = 0)
+int launch_cheb_x(pb_grid* g, const double* y, const double* ym1, const double* q, double* y_out,
+                  const CgState* st, double scale);
 // preonly: dst = dinv src (dst == nullptr: src as it is) with its sum per block; x -= sum / ntot
 // from the reduced sum in ctx->d_scalars[0]
 int launch_pre_scale_sum(pb_grid* g, const double* src, double* dst, double dinv, int* nparts);

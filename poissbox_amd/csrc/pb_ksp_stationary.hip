@@ -1,10 +1,13 @@
 // pb_ksp_stationary.hip -- the vector kernels and the one-block finalize of the stationary solves:
 // -ksp_type richardson (PETSc KSPSolve_Richardson: x += scale N(M^-1 (b - A x)), PC_LEFT, the
 // preconditioned norm, KSPConvergedDefault) and -ksp_type preonly (KSPSolve_PREONLY: x = N(M^-1 b)).
+// -ksp_type chebyshev (KSPSolve_Chebyshev) shares all of Richardson's but the update's expression
+// from its second update on and the omega recurrence in the finalize.
 // The hot step of Richardson on the 7-point operator is one stencil-engine pass (RichLoad /
-// RichEpi, pb_stencil.hip); the kernels here are its unfused form, the steps around operators
-// without an engine (compact, assembled, split grids) and the scalar logic. The device-resident
-// state, done flag, history and polling are CG's (CgState, pb_solver.cpp).
+// RichEpi, pb_stencil.hip; Chebyshev: ChebLoad / RichEpi); the kernels here are its unfused form,
+// the steps around operators without an engine (compact, assembled, split grids) and the scalar
+// logic. The device-resident state, done flag, history and polling are CG's (CgState,
+// pb_solver.cpp).
 #include "pb_cg_device.hpp"
 
 namespace pb {
@@ -19,7 +22,8 @@ namespace pb {
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void rich_stage(CgState& st, const double* S, bool setup, int ref,
                                            double bnorm, double* hist, int* h_done,
-                                           int64_t host_iter) {
+                                           int64_t host_iter, double cheb_mu,
+                                           double cheb_omegaprod) {
   if (setup) {
     st.it = 0;
     st.its = 0;
@@ -68,6 +72,14 @@ __device__ __forceinline__ void rich_stage(CgState& st, const double* S, bool se
       st.done = 1;
     } else {
       st.mu = st.mu + delta;
+      if (cheb_mu != 0.0) {
+        // -ksp_type chebyshev: update i follows; rho_i = c_i / c_(i+1) of PETSc's c_(k+1) =
+        // 2 mu c_k - c_(k-1) (which overflows in long runs), omega_i = omegaprod rho_i. Every
+        // setup restarts it (i = 0; update 0 is Richardson's and reads no omega)
+        const double rho = i == 0 ? 1.0 / cheb_mu : 1.0 / (2.0 * cheb_mu - st.beta);
+        st.beta = rho;
+        st.alpha = cheb_omegaprod * rho;
+      }
     }
   }
   h_done[setup ? 0 : host_iter + 1] = st.done;
@@ -80,7 +92,8 @@ __global__ __launch_bounds__(256) void rich_finalize_kernel(const double* __rest
                                                             int nparts, int width, double* sums,
                                                             int mode, const double* bsums, int ref,
                                                             CgState* st, double* hist, int* h_done,
-                                                            int64_t host_iter) {
+                                                            int64_t host_iter, double cheb_mu,
+                                                            double cheb_omegaprod) {
   if (mode & 1) {
     __shared__ double red[256][2];
     for (int s = 0; s < 2; ++s) {
@@ -111,7 +124,7 @@ __global__ __launch_bounds__(256) void rich_finalize_kernel(const double* __rest
     }
     bnorm = norm_from_sq(zz);
   }
-  rich_stage(*st, S, setup, ref, bnorm, hist, h_done, host_iter);
+  rich_stage(*st, S, setup, ref, bnorm, hist, h_done, host_iter, cheb_mu, cheb_omegaprod);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -130,6 +143,27 @@ __global__ __launch_bounds__(256) void rich_x_kernel(const double* __restrict__ 
     z = z + shift;
     const double u = scale * z;
     x_out[i] = x[i] + u;
+  }
+}
+
+// Chebyshev's update i >= 1, ChebLoad's expression (pb_stencil.hip) in its rounding order
+__global__ __launch_bounds__(256) void cheb_x_kernel(const double* __restrict__ y,
+                                                     const double* __restrict__ ym1,
+                                                     const double* __restrict__ q,
+                                                     double* __restrict__ y_out, int64_t n,
+                                                     const CgState* st, double scale) {
+  if (st->done) return;
+  const double dinv = st->dinv, shift = -st->mu, omega = st->alpha;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double z = dinv * q[i];
+    z = z + shift;
+    const double ykm1 = ym1[i];
+    double t = y[i] - ykm1;
+    const double u = scale * z;
+    t = t + u;
+    t = omega * t;
+    y_out[i] = t + ykm1;
   }
 }
 
@@ -208,6 +242,15 @@ int launch_rich_x(pb_grid* g, const double* x, const double* q, double* x_out, c
   return PB_OK;
 }
 
+int launch_cheb_x(pb_grid* g, const double* y, const double* ym1, const double* q, double* y_out,
+                  const CgState* st, double scale) {
+  ScopedTimer tm(g->ctx, "cheb_axpy");
+  hipLaunchKernelGGL(cheb_x_kernel, dim3(vec_blocks(g->ctx, g->nlocal)), dim3(256), 0,
+                     g->ctx->stream, y, ym1, q, y_out, g->nlocal, st, scale);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
 int launch_rich_resid(pb_grid* g, const double* b, const double* w, double* r, const CgState* st,
                       bool skip, int* nparts) {
   ScopedTimer tm(g->ctx, "rich_resid_vec");
@@ -237,7 +280,7 @@ int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst) {
   hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      (const double*)ctx->d_partials, nparts, width, ctx->d_scalars, 1,
                      (const double*)nullptr, 0, (CgState*)nullptr, (double*)nullptr,
-                     (int*)nullptr, (int64_t)0);
+                     (int*)nullptr, (int64_t)0, 0.0, 0.0);
   PB_HIP(hipGetLastError());
   if (ctx->split) PB_TRY(allreduce_device(ctx, ctx->d_scalars, 2));
   if (dst)
@@ -247,17 +290,20 @@ int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst) {
 }
 
 int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
-                  double* hist, int* h_done, int64_t host_iter) {
+                  double* hist, int* h_done, int64_t host_iter, double cheb_mu,
+                  double cheb_omegaprod) {
   const double* parts = ctx->d_partials;
   if (!ctx->split) {
     hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
-                       width, ctx->d_scalars, 3, bsums, ref, st, hist, h_done, host_iter);
+                       width, ctx->d_scalars, 3, bsums, ref, st, hist, h_done, host_iter, cheb_mu,
+                       cheb_omegaprod);
     PB_HIP(hipGetLastError());
     return PB_OK;
   }
   PB_TRY(rich_reduce(ctx, nparts, width, nullptr));
   hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
-                     width, ctx->d_scalars, 2, bsums, ref, st, hist, h_done, host_iter);
+                     width, ctx->d_scalars, 2, bsums, ref, st, hist, h_done, host_iter, cheb_mu,
+                     cheb_omegaprod);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }

@@ -47,8 +47,23 @@ struct pb_ksp {
   // r ping-pongs likewise (rich_rbuf), r_0 = b read in place from a zero guess
   double* x2 = nullptr;
   bool rich_guess = false;  // this solve started from a nonzero guess (r_0 is in r, not b)
-  bool rich() const { return opts.ksp_type == PB_KSP_RICHARDSON; }
-  double* xbuf(int64_t i) const { return (i & 1) ? x2 : x->d; }
+  // Chebyshev (-ksp_type chebyshev) runs as Richardson does (rich() covers both) with one more
+  // solution buffer: update i >= 1 reads y_i = xbuf(i) and y_(i-1) = xbuf(i - 1) and writes
+  // xbuf(i + 1), the three rotating; the caller's x is xbuf(0 mod 3)
+  double* x3 = nullptr;
+  bool cheb() const { return opts.ksp_type == PB_KSP_CHEBYSHEV; }
+  bool rich() const { return opts.ksp_type == PB_KSP_RICHARDSON || cheb(); }
+  double* xbuf(int64_t i) const {
+    if (cheb()) return i % 3 == 0 ? x->d : (i % 3 == 1 ? x2 : x3);
+    return (i & 1) ? x2 : x->d;
+  }
+  // the bounds in use and what follows from them (KSPSolve_Chebyshev's scale, mu, omegaprod);
+  // cheb_state: 0 = not set yet, 1 = the caller's, 2 = estimated for the deltas in cheb_deltas
+  // (A's, then P's: the estimate runs again when either changed)
+  pb_ksp_chebyshev_opts copts;  // pb_ksp_chebyshev_set_opts; the defaults from pb_ksp_create
+  int cheb_state = 0;
+  double cheb_emin = 0.0, cheb_emax = 0.0, cheb_scale = 0.0, cheb_mu = 0.0, cheb_omegaprod = 0.0;
+  double cheb_deltas[6] = {0, 0, 0, 0, 0, 0};
   const double* rich_rbuf(int64_t i) const {
     return i == 0 && !rich_guess ? b->d : ((i & 1) ? r2 : r);
   }
@@ -246,6 +261,54 @@ int pb_ksp_opts_default(pb_ksp_opts* o) {
   return PB_OK;
 }
 
+int pb_ksp_chebyshev_opts_default(pb_ksp_chebyshev_opts* o) {
+  PB_CHECK_ARG(o, "opts is NULL");
+  o->emin = 0.0;  // 0, 0: estimate
+  o->emax = 0.0;
+  const double tr[4] = {0.0, 0.1, 0.0, 1.1};  // KSPChebyshevEstEigSet's default transform
+  for (int i = 0; i < 4; ++i) o->esteig[i] = tr[i];
+  o->esteig_steps = 10;
+  return PB_OK;
+}
+
+// Chebyshev's interval: finite, non-zero, of one sign (negative pairs are legal, as in PETSc: A is
+// negative semi-definite, so M^-1 A is negative without a PC), emax > emin
+static int check_cheb_pair(double emin, double emax, const char* what) {
+  if (!std::isfinite(emin) || !std::isfinite(emax) || emin == 0.0 || emax == 0.0 ||
+      (emin < 0.0) != (emax < 0.0) || !(emax > emin))
+    return set_error(PB_ERR_ARG,
+                     "%s: emin %g, emax %g are no finite, non-zero bounds of one sign with "
+                     "emax > emin", what, emin, emax);
+  return PB_OK;
+}
+
+static int check_cheb_opts(const pb_ksp_chebyshev_opts* o) {
+  if (o->emin != 0.0 || o->emax != 0.0)
+    PB_TRY(check_cheb_pair(o->emin, o->emax, "chebyshev eigenvalues"));
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(o->esteig[i]))
+      return set_error(PB_ERR_ARG, "chebyshev esteig[%d] is not finite", i);
+  if (o->esteig_steps < 1 || o->esteig_steps > 64)
+    return set_error(PB_ERR_ARG, "chebyshev esteig_steps %d outside 1..64", o->esteig_steps);
+  return PB_OK;
+}
+
+// exactly n comma-separated numbers
+static bool parse_real_list(const char* v, int n, double* out) {
+  for (int i = 0; i < n; ++i) {
+    char* end = nullptr;
+    out[i] = strtod(v, &end);
+    if (end == v) return false;
+    if (i + 1 < n) {
+      if (*end != ',') return false;
+      v = end + 1;
+    } else if (*end != '\0') {
+      return false;
+    }
+  }
+  return true;
+}
+
 static int check_guess_opts(int model, int maxl) {
   if (model == 2 || model == 3)
     return set_error(PB_ERR_UNSUPPORTED, "-ksp_guess_fischer_model %d: only model 1", model);
@@ -261,6 +324,56 @@ static int check_ref_norm_opts(const pb_ksp_opts* o) {
     return set_error(PB_ERR_ARG,
                      "-ksp_converged_use_initial_residual_norm and "
                      "-ksp_converged_use_min_initial_residual_norm exclude each other");
+  return PB_OK;
+}
+
+int pb_ksp_chebyshev_opts_parse(pb_ksp_chebyshev_opts* o, int argc, const char* const* argv) {
+  PB_CHECK_ARG(o, "opts is NULL");
+  for (int i = 0; i < argc; ++i) {
+    const char* a = argv[i];
+    const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+    auto flag = [&](int* out) {  // PetscOptionsBool, as in pb_ksp_opts_parse
+      auto is = [&](const char* w) { return v && !strcasecmp(v, w); };
+      *out = 1;
+      if (is("true") || is("yes") || is("on") || is("1")) {
+        ++i;
+      } else if (is("false") || is("no") || is("off") || is("0")) {
+        *out = 0;
+        ++i;
+      }
+    };
+    if (!strcmp(a, "-ksp_chebyshev_eigenvalues") && v) {
+      double e[2];
+      if (!parse_real_list(v, 2, e))
+        return set_error(PB_ERR_ARG, "-ksp_chebyshev_eigenvalues %s: expected emin,emax", v);
+      PB_TRY(check_cheb_pair(e[0], e[1], "-ksp_chebyshev_eigenvalues"));
+      o->emin = e[0];
+      o->emax = e[1];
+      ++i;
+    } else if (!strcmp(a, "-ksp_chebyshev_esteig") && v) {
+      double t[4];
+      if (!parse_real_list(v, 4, t))
+        return set_error(PB_ERR_ARG, "-ksp_chebyshev_esteig %s: expected a,b,c,d", v);
+      for (int j = 0; j < 4; ++j) {
+        if (!std::isfinite(t[j]))
+          return set_error(PB_ERR_ARG, "-ksp_chebyshev_esteig %s: not finite", v);
+        o->esteig[j] = t[j];
+      }
+      ++i;
+    } else if (!strcmp(a, "-ksp_chebyshev_esteig_steps") && v) {
+      const int n = atoi(v);
+      if (n < 1 || n > 64)
+        return set_error(PB_ERR_ARG, "-ksp_chebyshev_esteig_steps %s: outside 1..64", v);
+      o->esteig_steps = n;
+      ++i;
+    } else if (!strcmp(a, "-ksp_chebyshev_esteig_noisy")) {
+      int noisy = 1;
+      flag(&noisy);
+      if (!noisy)
+        return set_error(PB_ERR_UNSUPPORTED,
+                         "-ksp_chebyshev_esteig_noisy false: the estimate starts from noise");
+    }
+  }
   return PB_OK;
 }
 
@@ -285,8 +398,10 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
       if (!strcmp(v, "cg")) o->ksp_type = PB_KSP_CG;
       else if (!strcmp(v, "preonly")) o->ksp_type = PB_KSP_PREONLY;
       else if (!strcmp(v, "richardson")) o->ksp_type = PB_KSP_RICHARDSON;
+      else if (!strcmp(v, "chebyshev")) o->ksp_type = PB_KSP_CHEBYSHEV;
       else
-        return set_error(PB_ERR_UNSUPPORTED, "-ksp_type %s: only cg, preonly, richardson", v);
+        return set_error(PB_ERR_UNSUPPORTED,
+                         "-ksp_type %s: only cg, preonly, richardson, chebyshev", v);
       ++i;
     } else if (!strcmp(a, "-ksp_richardson_scale") && v) {
       o->richardson_scale = atof(v);
@@ -354,6 +469,11 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
       o->converged_reason = 1;
     }
   }
+  // the -ksp_chebyshev_* options: their errors are reported here too (the values belong to
+  // pb_ksp_chebyshev_opts_parse)
+  pb_ksp_chebyshev_opts co;
+  pb_ksp_chebyshev_opts_default(&co);
+  PB_TRY(pb_ksp_chebyshev_opts_parse(&co, argc, argv));
   return check_ref_norm_opts(o);
 }
 
@@ -379,8 +499,10 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
   if (k->opts.check_every < 1) k->opts.check_every = 8;
   if (check_ref_norm_opts(&k->opts) != PB_OK) return fail(PB_ERR_ARG);
   const int kt = k->opts.ksp_type;
-  if (kt != PB_KSP_CG && kt != PB_KSP_PREONLY && kt != PB_KSP_RICHARDSON)
+  if (kt != PB_KSP_CG && kt != PB_KSP_PREONLY && kt != PB_KSP_RICHARDSON &&
+      kt != PB_KSP_CHEBYSHEV)
     return fail(set_error(PB_ERR_UNSUPPORTED, "unknown ksp_type %d", kt));
+  pb_ksp_chebyshev_opts_default(&k->copts);
   if (!std::isfinite(k->opts.richardson_scale))
     return fail(set_error(PB_ERR_ARG, "richardson_scale is not finite"));
   if (kt == PB_KSP_PREONLY &&
@@ -545,7 +667,7 @@ static int guess_setup(pb_ksp* k, const double* b, const double* x0, double dinv
 }
 
 // ---------------------------------------------------------------------------------------------
-// Stationary solves: -ksp_type richardson, -ksp_type preonly
+// Stationary solves: -ksp_type richardson, chebyshev, preonly
 // ---------------------------------------------------------------------------------------------
 // the 7-point operator on one rank: the engine pass reads the periodic wrap planes in place
 static bool rich_engine(const pb_ksp* k) {
@@ -580,6 +702,131 @@ static int rich_pc(pb_ksp* k, const double* r, const int* skip, int* np) {
   return PB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Chebyshev's interval
+// ---------------------------------------------------------------------------------------------
+// z = N(M^-1 r) with the KSP's PC and null space, host-driven (setup cost, not a hot path)
+static int cheb_pc_n(pb_ksp* k, const double* r, double* z) {
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  if (k->mg) {
+    PB_TRY(mg_apply(k->mg, r, z));
+  } else if (k->fft) {
+    PB_TRY(fftpc_apply(k->fft, r, z));
+  } else {
+    PB_HIP(hipMemcpyAsync(z, r, (size_t)g->nlocal * sizeof(double), hipMemcpyDeviceToDevice,
+                          ctx->stream));
+    if (k->opts.pc_type == PB_PC_JACOBI)
+      PB_TRY(vec_update(ctx, 2, z, nullptr, g->nlocal, 1.0 / k->P->cc));
+  }
+  if (!k->opts.nullspace) return PB_OK;
+  int np = 0;
+  PB_TRY(launch_pre_scale_sum(g, z, nullptr, 1.0, &np));
+  PB_TRY(rich_reduce(ctx, np, 2, nullptr));
+  return launch_pre_shift(g, z, (double)(g->n[0] * g->n[1] * g->n[2]));
+}
+
+// The extreme eigenvalues of M^-1 A on the range of N from `steps` steps of preconditioned
+// CG-Lanczos (poissbox_gpu.h, pb_ksp_chebyshev_get_eigenvalues). Uses r, pb[0], pb[1] and x2:
+// nothing of a solve may be in them. *n_out = the steps the tridiagonal holds (0: none)
+static int cheb_lanczos(pb_ksp* k, double* lo, double* hi, int* n_out) {
+  pb_grid* g = k->A->grid;
+  pb_ctx* ctx = g->ctx;
+  const int64_t n = g->nlocal;
+  const size_t vb = (size_t)n * sizeof(double);
+  if (!k->x2 && field_alloc(&k->x2, vb) != hipSuccess)
+    return set_error(PB_ERR_ALLOC, "Chebyshev solution buffer: out of device memory");
+  double *r = k->r, *p = k->pb[0], *w = k->pb[1], *z = k->x2;
+  const int steps = k->copts.esteig_steps;
+  double diag[64], off[64], alpha_prev = 0.0, beta_prev = 0.0;
+  int m = 0;
+  PB_TRY(vec_random(ctx, r, n, PB_CHEBYSHEV_ESTEIG_SEED, g->k0 * g->plane));
+  if (k->opts.nullspace) {  // r_0 = N(v): r then stays in A's range
+    int np = 0;
+    PB_TRY(launch_pre_scale_sum(g, r, nullptr, 1.0, &np));
+    PB_TRY(rich_reduce(ctx, np, 2, nullptr));
+    PB_TRY(launch_pre_shift(g, r, (double)(g->n[0] * g->n[1] * g->n[2])));
+  }
+  PB_TRY(cheb_pc_n(k, r, z));
+  PB_HIP(hipMemcpyAsync(p, z, vb, hipMemcpyDeviceToDevice, ctx->stream));
+  double rz = 0.0, rz0 = 0.0;
+  PB_TRY(vec_reduce(ctx, 1, r, z, n, &rz));
+  rz0 = rz;
+  for (int j = 0; j < steps; ++j) {
+    double pw = 0.0;
+    PB_TRY(op_apply_raw(k->A, p, w));
+    PB_TRY(vec_reduce(ctx, 1, p, w, n, &pw));
+    const double alpha = rz / pw;
+    if (!std::isfinite(alpha) || alpha == 0.0) break;
+    diag[j] = 1.0 / alpha + (j > 0 ? beta_prev / alpha_prev : 0.0);
+    m = j + 1;
+    if (m == steps) break;
+    PB_TRY(vec_update(ctx, 0, r, w, n, -alpha));
+    PB_TRY(cheb_pc_n(k, r, z));
+    double rz_new = 0.0;
+    PB_TRY(vec_reduce(ctx, 1, r, z, n, &rz_new));
+    const double beta = rz_new / rz;
+    // the Krylov space is exhausted (-pc_type fft with A = P after one step), or the PC is not
+    // definite on it
+    if (!std::isfinite(beta) || beta <= 0.0 || std::fabs(rz_new) <= 1e-24 * std::fabs(rz0)) break;
+    off[j] = std::sqrt(beta) / alpha;
+    PB_TRY(vec_update(ctx, 1, p, z, n, beta));
+    alpha_prev = alpha;
+    beta_prev = beta;
+    rz = rz_new;
+  }
+  *n_out = m;
+  if (m == 0) return PB_OK;
+  return pb_tridiag_extreme_eigenvalues(m, diag, off, lo, hi);
+}
+
+// the bounds of the next solve into k->cheb_*: the caller's, or the estimate (run once per pair of
+// deltas) through the transform; an invalid pair is PB_ERR_ARG and leaves the KSP usable
+static int cheb_bounds(pb_ksp* k) {
+  const pb_ksp_chebyshev_opts& o = k->copts;
+  double emin = o.emin, emax = o.emax;
+  const bool given = emin != 0.0 || emax != 0.0;
+  double dl[6];
+  for (int d = 0; d < 3; ++d) {
+    dl[d] = k->A->deltas[d];
+    dl[3 + d] = k->P->deltas[d];
+  }
+  if (given) {
+    PB_TRY(check_cheb_pair(emin, emax, "chebyshev eigenvalues"));
+    k->cheb_state = 1;
+  } else if (k->cheb_state != 2 || memcmp(dl, k->cheb_deltas, sizeof(dl)) != 0) {
+    if (k->begun) return set_error(PB_ERR_STATE, "Chebyshev eigenvalue estimate inside a solve");
+    double lo = 0.0, hi = 0.0;
+    int m = 0;
+    k->cheb_state = 0;
+    PB_TRY(cheb_lanczos(k, &lo, &hi, &m));
+    if (m == 0)
+      return set_error(PB_ERR_ARG, "Chebyshev eigenvalue estimate: the Lanczos process broke down "
+                                   "at its first step");
+    emin = o.esteig[0] * lo + o.esteig[1] * hi;
+    emax = o.esteig[2] * lo + o.esteig[3] * hi;
+    if (check_cheb_pair(emin, emax, "estimate") != PB_OK)
+      return set_error(PB_ERR_ARG,
+                       "Chebyshev eigenvalue estimate: extremes %g, %g transform to emin %g, emax "
+                       "%g, no valid bounds (a negative spectrum, as with -pc_type none, needs "
+                       "-ksp_chebyshev_esteig weights that keep emax > emin, or explicit "
+                       "-ksp_chebyshev_eigenvalues)", lo, hi, emin, emax);
+    memcpy(k->cheb_deltas, dl, sizeof(dl));
+    k->cheb_state = 2;
+  } else {
+    emin = k->cheb_emin;
+    emax = k->cheb_emax;
+  }
+  k->cheb_emin = emin;
+  k->cheb_emax = emax;
+  // KSPSolve_Chebyshev's quantities
+  k->cheb_scale = 2.0 / (emax + emin);
+  const double alpha = 1.0 - k->cheb_scale * emin;
+  k->cheb_mu = 1.0 / alpha;
+  k->cheb_omegaprod = 2.0 / alpha;
+  return PB_OK;
+}
+
 // KSPSolve_Richardson's setup: r_0 = b (read in place), x_0 = 0, or r_0 = b - A x_0 from a nonzero
 // guess with CG's reference-norm rules; z_0, its norm, history[0] and the first test
 static int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
@@ -587,17 +834,24 @@ static int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   pb_ctx* ctx = g->ctx;
   const size_t vb = (size_t)g->nlocal * sizeof(double);
   // b is read by every update (r = b - A x) while x is written
-  PB_CHECK_ARG(b != x, "richardson needs distinct b and x");
+  PB_CHECK_ARG(b != x, k->cheb() ? "chebyshev needs distinct b and x"
+                                   : "richardson needs distinct b and x");
   k->sr = false;
   k->pst = false;
   k->lazy0 = false;
   k->defer_x = 0;
   if (!k->x2 && field_alloc(&k->x2, vb) != hipSuccess)
     return set_error(PB_ERR_ALLOC, "Richardson solution buffer: out of device memory");
+  if (k->cheb() && !k->x3 && field_alloc(&k->x3, vb) != hipSuccess)
+    return set_error(PB_ERR_ALLOC, "Chebyshev solution buffer: out of device memory");
   if (!k->stored_z() && !k->r2 && field_alloc(&k->r2, vb) != hipSuccess)
     return set_error(PB_ERR_ALLOC, "Richardson residual buffer: out of device memory");
   if (!rich_engine(k) && !k->w && field_alloc(&k->w, vb) != hipSuccess)
     return set_error(PB_ERR_ALLOC, "Richardson work vector: out of device memory");
+  // (the eigenvalue estimate, when it has to run, uses the work vectors: before anything of
+  // this solve is in them; invalid bounds leave the KSP as it was)
+  if (k->cheb()) PB_TRY(cheb_bounds(k));
+  const double cmu = k->cheb() ? k->cheb_mu : 0.0, cop = k->cheb() ? k->cheb_omegaprod : 0.0;
   k->b = b;
   k->x = x;
   k->rich_guess = k->opts.initial_guess_nonzero != 0;
@@ -607,7 +861,8 @@ static int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
     PB_HIP(hipMemsetAsync(x->d, 0, vb, ctx->stream));
     if (k->stored_z()) PB_TRY(rich_pc(k, b->d, nullptr, &np));
     else PB_TRY(launch_rich_sums(g, b->d, k->d_st, &np));
-    return rich_finalize(ctx, np, width, nullptr, 3, k->d_st, k->d_hist, k->h_done_dev, -1);
+    return rich_finalize(ctx, np, width, nullptr, 3, k->d_st, k->d_hist, k->h_done_dev, -1, cmu,
+                         cop);
   }
   PB_TRY(check_ref_norm_opts(&k->opts));
   const int ref = k->opts.converged_use_initial_residual_norm
@@ -622,7 +877,8 @@ static int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   }
   PB_TRY(rich_residual(k, x->d, k->r, false, &np));
   if (k->stored_z()) PB_TRY(rich_pc(k, k->r, nullptr, &np));
-  return rich_finalize(ctx, np, width, bsums, ref, k->d_st, k->d_hist, k->h_done_dev, -1);
+  return rich_finalize(ctx, np, width, bsums, ref, k->d_st, k->d_hist, k->h_done_dev, -1, cmu,
+                       cop);
 }
 
 // one update: x_new = x + scale (M^-1 r - mean), r_new = b - A x_new, z_new and its sums, the
@@ -636,22 +892,33 @@ static int enqueue_rich_iteration(pb_ksp* k) {
   double* xout = k->xbuf(i + 1);
   const double* q = k->stored_z() ? k->z : k->rich_rbuf(i);
   double* r_out = k->stored_z() ? k->r : (((i + 1) & 1) ? k->r2 : k->r);
-  const double scale = k->opts.richardson_scale;
+  // Chebyshev: update 0 is Richardson's with scale = 2 / (emax + emin); update i >= 1 reads
+  // y_(i-1) too (host_iter is the device's update count while the state is not done, and every
+  // launch of a done state exits at entry)
+  const bool cheb = k->cheb();
+  const double scale = cheb ? k->cheb_scale : k->opts.richardson_scale;
+  const double* xm1 = cheb && i >= 1 ? k->xbuf(i - 1) : nullptr;
+  const bool fused = rich_engine(k) && (cheb ? tune("cheb_fused", 1) : tune("rich_fused", 1)) != 0;
   int np = 0;
-  if (rich_engine(k) && tune("rich_fused", 1) != 0) {
+  if (fused) {
     Star s{k->A->cx, k->A->cy, k->A->cz, k->A->cc};
     StencilPlanes gp;
     gp.ghost_lo = gp.ghost_hi = nullptr;
     gp.wrap = true;
-    PB_TRY(launch_rich_update(g, s, xin, q, k->b->d, xout, r_out, gp, k->d_st, scale,
-                              !k->stored_z(), true, &np));
+    if (xm1)
+      PB_TRY(launch_cheb_update(g, s, xin, xm1, q, k->b->d, xout, r_out, gp, k->d_st, scale,
+                                !k->stored_z(), &np));
+    else
+      PB_TRY(launch_rich_update(g, s, xin, q, k->b->d, xout, r_out, gp, k->d_st, scale,
+                                !k->stored_z(), true, &np));
   } else {
-    PB_TRY(launch_rich_x(g, xin, q, xout, k->d_st, scale));
+    if (xm1) PB_TRY(launch_cheb_x(g, xin, xm1, q, xout, k->d_st, scale));
+    else PB_TRY(launch_rich_x(g, xin, q, xout, k->d_st, scale));
     PB_TRY(rich_residual(k, xout, r_out, true, &np));
   }
   if (k->stored_z()) PB_TRY(rich_pc(k, r_out, &k->d_st->done, &np));
   return rich_finalize(ctx, np, k->stored_z() ? 4 : 2, nullptr, 0, k->d_st, k->d_hist,
-                       k->h_done_dev, i);
+                       k->h_done_dev, i, cheb ? k->cheb_mu : 0.0, cheb ? k->cheb_omegaprod : 0.0);
 }
 
 // KSPSolve_PREONLY: x = N(M^-1 b). No norm, no reduction but the mean's, no NaN check. The
@@ -1253,8 +1520,10 @@ int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
   CgState st;
   PB_HIP(hipMemcpyAsync(&st, k->d_st, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
   PB_SYNC(ctx, "pb_ksp_end");
-  if (k->rich() && (st.its & 1)) {  // an odd number of updates: the result is in the other buffer
-    PB_HIP(hipMemcpyAsync(k->x->d, k->x2, (size_t)k->A->grid->nlocal * sizeof(double),
+  // Richardson after an odd number of updates, Chebyshev after one that is no multiple of 3: the
+  // result is in another buffer than the caller's
+  if (k->rich() && k->xbuf(st.its) != k->x->d) {
+    PB_HIP(hipMemcpyAsync(k->x->d, k->xbuf(st.its), (size_t)k->A->grid->nlocal * sizeof(double),
                           hipMemcpyDeviceToDevice, ctx->stream));
     PB_SYNC(ctx, "pb_ksp_end");
   }
@@ -1461,6 +1730,7 @@ int pb_ksp_destroy(pb_ksp* k) {
   field_free(k->w);
   field_free(k->z);
   field_free(k->x2);
+  field_free(k->x3);
   if (k->mg) mg_destroy(k->mg);
   fftpc_destroy(k->fft);
   if (k->fg) {
@@ -1503,8 +1773,78 @@ int pb_ksp_pc_levels(const pb_ksp* k, int* levels) {
   return PB_OK;
 }
 
+int pb_ksp_chebyshev_set_opts(pb_ksp* k, const pb_ksp_chebyshev_opts* o) {
+  PB_CHECK_ARG(k && o, "bad args");
+  if (!k->cheb()) return set_error(PB_ERR_STATE, "KSP created without -ksp_type chebyshev");
+  if (k->begun) return set_error(PB_ERR_STATE, "pb_ksp_chebyshev_set_opts inside a solve");
+  PB_TRY(check_cheb_opts(o));
+  k->copts = *o;
+  k->cheb_state = 0;
+  return PB_OK;
+}
+
+int pb_ksp_chebyshev_get_eigenvalues(pb_ksp* k, double* emin, double* emax, int* estimated) {
+  PB_CHECK_ARG(k, "ksp is NULL");
+  if (!k->cheb()) return set_error(PB_ERR_STATE, "KSP created without -ksp_type chebyshev");
+  PB_TRY(cheb_bounds(k));
+  PB_SYNC(k->A->grid->ctx, "pb_ksp_chebyshev_get_eigenvalues");
+  if (emin) *emin = k->cheb_emin;
+  if (emax) *emax = k->cheb_emax;
+  if (estimated) *estimated = k->cheb_state == 2 ? 1 : 0;
+  return PB_OK;
+}
+
+// Bisection on the Sturm count (the number of eigenvalues below s = the number of negative pivots
+// of T - s I), started from the Gershgorin interval; ends when the interval cannot be halved
+int pb_tridiag_extreme_eigenvalues(int n, const double* diag, const double* off, double* lo,
+                                   double* hi) {
+  PB_CHECK_ARG(n >= 1 && n <= 64, "tridiagonal order outside 1..64");
+  PB_CHECK_ARG(diag && lo && hi && (off || n == 1), "bad tridiagonal args");
+  double gl = INFINITY, gu = -INFINITY;
+  for (int i = 0; i < n; ++i) {
+    const double a = i > 0 ? std::fabs(off[i - 1]) : 0.0, c = i + 1 < n ? std::fabs(off[i]) : 0.0;
+    PB_CHECK_ARG(std::isfinite(diag[i]) && std::isfinite(a) && std::isfinite(c),
+                 "tridiagonal entries must be finite");
+    gl = std::min(gl, diag[i] - (a + c));
+    gu = std::max(gu, diag[i] + (a + c));
+  }
+  PB_CHECK_ARG(std::isfinite(gl) && std::isfinite(gu), "tridiagonal entries too large");
+  const double tiny = 1e-300 + 2.3e-16 * std::max(std::fabs(gl), std::fabs(gu));
+  auto below = [&](double s) {
+    int cnt = 0;
+    double q = 1.0;
+    for (int i = 0; i < n; ++i) {
+      const double e = i > 0 ? off[i - 1] : 0.0;
+      q = diag[i] - s - (i > 0 ? e * e / q : 0.0);
+      if (std::fabs(q) < tiny) q = -tiny;
+      if (q < 0.0) ++cnt;
+    }
+    return cnt;
+  };
+  // the index-th eigenvalue (ascending): the s where below(s) passes from <= index to > index
+  auto kth = [&](int index) {
+    double a = gl, b = gu;
+    for (int it = 0; it < 2000; ++it) {
+      const double m = a + 0.5 * (b - a);
+      if (!(m > a && m < b)) break;
+      if (below(m) > index) b = m;
+      else a = m;
+    }
+    return a + 0.5 * (b - a);
+  };
+  *lo = kth(0);
+  *hi = kth(n - 1);
+  return PB_OK;
+}
+
 int pb_solve(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_vec* b, pb_vec* x,
              pb_ksp_result* res, double* history, int64_t cap) {
+  return pb_solve_chebyshev(A, P, opts, nullptr, b, x, res, history, cap);
+}
+
+int pb_solve_chebyshev(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
+                       const pb_ksp_chebyshev_opts* cheb, const pb_vec* b, pb_vec* x,
+                       pb_ksp_result* res, double* history, int64_t cap) {
   pb_ksp* k = nullptr;
   pb_ksp_opts one;
   if (opts && opts->guess_type == PB_GUESS_FISCHER) {
@@ -1515,9 +1855,11 @@ int pb_solve(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_vec* b, pb_ve
     opts = &one;
   }
   PB_TRY(pb_ksp_create(A, P, opts, &k));
-  int rc = pb_ksp_solve(k, b, x, res, history, cap);
+  int rc = cheb && k->cheb() ? pb_ksp_chebyshev_set_opts(k, cheb) : PB_OK;
+  if (rc == PB_OK) rc = pb_ksp_solve(k, b, x, res, history, cap);
+  const std::string msg = rc != PB_OK ? pb_last_error() : "";
   pb_ksp_destroy(k);
-  return rc;
+  return rc != PB_OK ? set_error(rc, "%s", msg.c_str()) : PB_OK;
 }
 
 }  // extern "C"

@@ -358,6 +358,39 @@ struct RichLoad {
     return raw[0] + u;
   }
 };
+// Chebyshev (-ksp_type chebyshev, PETSc KSPSolve_Chebyshev), update i >= 1: the field is
+// y_new = omega ((y - ym1) + scale (dinv q + shift)) + ym1, formed on load from three raw arrays
+// (omega = the state's alpha, advanced by the finalize before this pass), every operation rounded
+// in this order; cheb_x_kernel (pb_ksp_stationary.hip) is the same expression. RichEpi stores
+// y_new and r_new = b - A y_new: reads y, ym1, q, b and writes y, r, 48 B/DoF. y_new goes to a
+// third buffer: neighbouring waves and blocks still read y and ym1 around this point.
+struct ChebLoad {
+  static constexpr int NR = 3;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ y;
+  const double* __restrict__ ym1;
+  const double* __restrict__ q;
+  const CgState* st;
+  double scale;
+  double dinv = 1.0, shift = 0.0, omega = 0.0;
+  __device__ __forceinline__ void prepare() {
+    dinv = st->dinv;
+    shift = -st->mu;
+    omega = st->alpha;
+  }
+  __device__ __forceinline__ const double* src(int a) const {
+    return a == 0 ? y : (a == 1 ? ym1 : q);
+  }
+  __device__ __forceinline__ double value(const double* raw) const {
+    double z = dinv * raw[2];
+    z = z + shift;
+    double t = raw[0] - raw[1];
+    const double u = scale * z;
+    t = t + u;
+    t = omega * t;
+    return t + raw[1];
+  }
+};
 template <bool STOREX, bool SUMS>
 struct RichEpi {
   static constexpr int NS = SUMS ? 2 : 0, NE = 1;
@@ -1210,6 +1243,21 @@ int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double*
     return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, true>{nullptr, r_out, b, st}, sk,
                       PLANES_ALL, 0, nparts);
   return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, false>{nullptr, r_out, b, st}, sk);
+}
+
+// Chebyshev's update + residual pass for updates i >= 1 (ChebLoad / RichEpi), whole grid, wrap
+// planes; always an iteration's launch (exits at entry once the state is done)
+int launch_cheb_update(pb_grid* g, const Star& s, const double* y, const double* ym1,
+                       const double* q, const double* b, double* y_out, double* r_out,
+                       const StencilPlanes& gp, const CgState* st, double scale, bool sums,
+                       int* nparts) {
+  ScopedTimer tm(g->ctx, "cheb_update");
+  *nparts = 0;
+  const ChebLoad ld{y, ym1, q, st, scale};
+  if (sums)
+    return launch_any(g, s, ld, gp, RichEpi<true, true>{y_out, r_out, b, st}, &st->done,
+                      PLANES_ALL, 0, nparts);
+  return launch_any(g, s, ld, gp, RichEpi<true, false>{y_out, r_out, b, st}, &st->done);
 }
 
 // cg_finalize_kernel's stage 0 for a setup from a nonzero guess: reduces `width` (4 or 6) sums per

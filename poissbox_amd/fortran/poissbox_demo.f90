@@ -7,6 +7,9 @@
 ! (`torchrun --no-python --nproc-per-node N poissbox_demo ...`, mpirun, or RANK/WORLD_SIZE set by
 ! hand): the per-rank lines reproduce README.md:25-33 (64^3 on 3 ranks: 90112/86016/86016).
 ! Usage: poissbox_demo [-n N] [-ksp_rtol 1e-10] [-ksp_monitor] [-ksp_converged_reason] ...
+! Every option of pb_ksp_opts_parse is accepted (solve passes the command line on), e.g.
+!   -ksp_type chebyshev -pc_type mg                      (bounds estimated)
+!   -ksp_type chebyshev -ksp_chebyshev_eigenvalues 0.05,2.0 -ksp_chebyshev_esteig_steps 20
 program poissbox_demo
 
   use iso_c_binding, only: c_int64_t

@@ -65,6 +65,13 @@ module poissbox_gpu
      real(c_double) :: richardson_scale      ! -ksp_richardson_scale (default 1.0)
   end type pb_ksp_opts
 
+  !! -ksp_type chebyshev's settings (a struct of their own: pb_ksp_chebyshev_set_opts)
+  type, bind(C), public :: pb_ksp_chebyshev_opts
+     real(c_double) :: emin, emax            ! -ksp_chebyshev_eigenvalues (0, 0: estimate)
+     real(c_double) :: esteig(4)             ! -ksp_chebyshev_esteig a,b,c,d (0, 0.1, 0, 1.1)
+     integer(c_int) :: esteig_steps          ! -ksp_chebyshev_esteig_steps (10)
+  end type pb_ksp_chebyshev_opts
+
   type, bind(C), public :: pb_ksp_result
      integer(c_int) :: reason
      integer(c_int64_t) :: its
@@ -90,6 +97,11 @@ module poissbox_gpu
   public :: c_pb_tdma_batched_host, c_pb_tdma_sweeps_batched_host, c_pb_compact_1d_batched_host
   public :: c_pb_compact_grad_host, c_pb_compact_div_host, c_pb_compact_interp_host
   public :: c_pb_compact_lapl_host, c_pb_lapl_1d_coeffs, c_pb_lapl_star_coeffs
+  ! -ksp_type chebyshev: the bounds a KSP uses (estimating them if need be), and the host routine
+  ! behind the estimate
+  public :: c_pb_ksp_chebyshev_get_eigenvalues, c_pb_tridiag_extreme_eigenvalues
+  public :: c_pb_ksp_chebyshev_opts_default, c_pb_ksp_chebyshev_opts_parse
+  public :: c_pb_ksp_chebyshev_set_opts, c_pb_solve_chebyshev
 
   interface PoissboxAllreduceSum  ! ≙ MPI_Allreduce(..., MPI_SUM, MPI_COMM_WORLD)
      module procedure allreduce_sum_int, allreduce_sum_real
@@ -417,6 +429,47 @@ module poissbox_gpu
        type(c_ptr), value :: ksp
        integer(c_int) :: curl, maxl
      end function
+     integer(c_int) function c_pb_ksp_chebyshev_opts_default(o) &
+          bind(C, name="pb_ksp_chebyshev_opts_default")
+       import :: c_int, pb_ksp_chebyshev_opts
+       type(pb_ksp_chebyshev_opts) :: o
+     end function
+     integer(c_int) function c_pb_ksp_chebyshev_opts_parse(o, argc, argv) &
+          bind(C, name="pb_ksp_chebyshev_opts_parse")
+       import :: c_int, c_ptr, pb_ksp_chebyshev_opts
+       type(pb_ksp_chebyshev_opts) :: o
+       integer(c_int), value :: argc
+       type(c_ptr), dimension(*) :: argv
+     end function
+     integer(c_int) function c_pb_ksp_chebyshev_set_opts(ksp, o) &
+          bind(C, name="pb_ksp_chebyshev_set_opts")
+       import :: c_int, c_ptr, pb_ksp_chebyshev_opts
+       type(c_ptr), value :: ksp
+       type(pb_ksp_chebyshev_opts) :: o
+     end function
+     integer(c_int) function c_pb_solve_chebyshev(A, P, o, co, b, x, res, hist, cap) &
+          bind(C, name="pb_solve_chebyshev")
+       import :: c_int, c_ptr, c_int64_t, pb_ksp_opts, pb_ksp_chebyshev_opts, pb_ksp_result
+       type(c_ptr), value :: A, P, b, x, hist
+       type(pb_ksp_opts) :: o
+       type(pb_ksp_chebyshev_opts) :: co
+       type(pb_ksp_result) :: res
+       integer(c_int64_t), value :: cap
+     end function
+     integer(c_int) function c_pb_ksp_chebyshev_get_eigenvalues(ksp, emin, emax, estimated) &
+          bind(C, name="pb_ksp_chebyshev_get_eigenvalues")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ksp
+       real(c_double) :: emin, emax
+       integer(c_int) :: estimated
+     end function
+     integer(c_int) function c_pb_tridiag_extreme_eigenvalues(n, diag, off, lo, hi) &
+          bind(C, name="pb_tridiag_extreme_eigenvalues")
+       import :: c_int, c_double
+       integer(c_int), value :: n
+       real(c_double) :: diag(*), off(*)
+       real(c_double) :: lo, hi
+     end function
   end interface
 
 contains
@@ -656,6 +709,7 @@ contains
     integer, intent(out), optional :: its, reason
     real(pb_dp), intent(out), optional :: rnorm
     type(pb_ksp_opts) :: o
+    type(pb_ksp_chebyshev_opts) :: co
     type(pb_ksp_result) :: res
     integer :: nargs, i, l, lmax
     character(len=:), allocatable, target :: args(:)
@@ -676,12 +730,15 @@ contains
        argv(i) = c_loc(args(i))
     end do
     ierr = c_pb_ksp_opts_parse(o, int(nargs, c_int), argv)
+    if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_default(co)
+    if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_parse(co, int(nargs, c_int), argv)
     if (ierr /= 0) then
        call check(ierr, "KSPSetFromOptions")
        return
     end if
     if (c_associated(A%h, P%h) .eqv. .false.) print *, "Setting nullspace on A"
-    ierr = c_pb_solve(A%h, P%h, o, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
+    ! (the Chebyshev settings are read by a KSP of that type only)
+    ierr = c_pb_solve_chebyshev(A%h, P%h, o, co, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
     call check(ierr, "KSPSolve")
     if (present(its)) its = int(res%its)
     if (present(reason)) reason = int(res%reason)
