@@ -329,6 +329,37 @@ typedef struct {
                         PB_ERR_ARG), default 10. -ksp_chebyshev_esteig_noisy false is
                         PB_ERR_UNSUPPORTED: the estimate always starts from noise */
 } pb_ksp_chebyshev_opts;
+/* The level smoother of PB_PC_MG (PETSc's -mg_levels_* family; the reference README.md:43-44
+ * puts richardson + sor on the levels). Like pb_ksp_chebyshev_opts a struct of its own, set on the
+ * KSP after pb_ksp_create (pb_ksp_pc_mg_set_opts): a KSP that was given none, or the defaults,
+ * runs the V(1,1) red-black SOR cycle with its fused passes, one-launch tail and agglomeration.
+ *  richardson + sor: max_it red-black sweeps per leg, pre-smoothing max_it x (red, black),
+ *    post-smoothing max_it x (black, red), omega = -pc_sor_omega. levels_richardson_scale must
+ *    be 1 (else PB_ERR_UNSUPPORTED).
+ *  richardson + jacobi: damped Jacobi, y += s D^-1 (b - A y), s = levels_richardson_scale.
+ *  chebyshev + jacobi: PB_KSP_CHEBYSHEV's recurrence above with M = D, restarted at every
+ *    smoothing call (rho_0 = 1 / mu), no null-space projection, no norm:
+ *    y_1 = y_0 + scale D^-1 r_0, y_(i+1) = omega_i ((y_i - y_(i-1)) + scale D^-1 r_i) + y_(i-1),
+ *    every operation rounded. Pre-smoothing starts from zero (y_1 = scale D^-1 b).
+ *  chebyshev + sor: PB_ERR_UNSUPPORTED.
+ * Bounds of chebyshev: levels_eigenvalues, or (0, 0) the esteig transform of (0, 2) -- D^-1 A of
+ * the periodic 7-point operator with even extents has the smallest eigenvalue 0 and the largest
+ * exactly 2 on every level, so emin = 2 b, emax = 2 d: [0.2, 2.2] by default. Deviation from
+ * PETSc, which estimates the largest eigenvalue with a Krylov run per level: no estimation pass
+ * runs here, the bounds are the same on every level, every rank and every run.
+ * A non-default smoother (or max_it > 1) runs per-level launches: the one-launch coarse tail and
+ * the agglomerated coarse levels of a decomposed grid are bypassed. The coarsest level stays
+ * -pc_mg_coarse_its symmetric red-black SOR sweeps whatever the level smoother is. */
+enum pb_mg_levels_ksp { PB_MG_LEVELS_RICHARDSON = 0, PB_MG_LEVELS_CHEBYSHEV = 1 };
+enum pb_mg_levels_pc { PB_MG_LEVELS_SOR = 0, PB_MG_LEVELS_JACOBI = 1 };
+typedef struct {
+  int levels_ksp_type;      /* -mg_levels_ksp_type richardson|chebyshev   (richardson) */
+  int levels_pc_type;       /* -mg_levels_pc_type sor|jacobi              (sor)        */
+  int levels_ksp_max_it;    /* -mg_levels_ksp_max_it: sweeps / steps per leg, 1..8 (1)  */
+  double levels_richardson_scale; /* -mg_levels_ksp_richardson_scale (1.0), finite, > 0 */
+  double levels_eigenvalues[2];   /* -mg_levels_ksp_chebyshev_eigenvalues emin,emax; 0,0: derive */
+  double levels_esteig[4];        /* -mg_levels_ksp_chebyshev_esteig a,b,c,d (0, 0.1, 0, 1.1) */
+} pb_pc_mg_opts;
 typedef struct {
   int reason;
   int64_t its;
@@ -347,6 +378,8 @@ int pb_ksp_opts_default(pb_ksp_opts* opts);
  * -ksp_guess_fischer_model <model>[,<maxl>]; unknown options are ignored. The -ksp_chebyshev_*
  * options are checked here as pb_ksp_chebyshev_opts_parse checks them (the same errors), but
  * their values are kept by that call only.
+ * Likewise the -mg_levels_* options of -pc_type mg's level smoother: checked here, kept by
+ * pb_pc_mg_opts_parse only.
  * -pc_type sor: one symmetric red-black SOR sweep (PETSc PCSOR default: 1 local symmetric sweep,
  * here in red-black order). -pc_type mg (or gamg): geometric V(1,1) multigrid with red-black SOR
  * smoothing on the 7-point P (README.md:40-45 recommends GAMG + SOR). Both need even extents. */
@@ -380,6 +413,24 @@ int pb_ksp_chebyshev_set_opts(pb_ksp* ksp, const pb_ksp_chebyshev_opts* opts);
 int pb_solve_chebyshev(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
                        const pb_ksp_chebyshev_opts* cheb, const pb_vec* b, pb_vec* x,
                        pb_ksp_result* res, double* history, int64_t history_cap);
+/* -mg_levels_ksp_type, -mg_levels_pc_type, -mg_levels_ksp_max_it,
+ * -mg_levels_ksp_richardson_scale, -mg_levels_ksp_chebyshev_eigenvalues emin,emax and
+ * -mg_levels_ksp_chebyshev_esteig a,b,c,d from the same argument list as pb_ksp_opts_parse (which
+ * reports the same errors and keeps no value); other options are ignored. -mg_levels_ksp_rtol
+ * and -mg_coarse_sub_pc_type are accepted and have no effect: the sweep count is fixed and the
+ * coarsest level runs -pc_mg_coarse_its SOR sweeps. Bounds that are given must be finite and
+ * positive with emax > emin (PB_ERR_ARG: D^-1 A is positive semi-definite). */
+int pb_pc_mg_opts_default(pb_pc_mg_opts* opts);
+int pb_pc_mg_opts_parse(pb_pc_mg_opts* opts, int argc, const char* const* argv);
+/* Sets them on a KSP with pc_type PB_PC_MG (PB_ERR_STATE on another PC or inside a solve;
+ * PB_ERR_ARG / PB_ERR_UNSUPPORTED for invalid values, which leave the KSP as it was). The
+ * Jacobi-type smoothers' extra level arrays are allocated here, not at pb_ksp_create. */
+int pb_ksp_pc_mg_set_opts(pb_ksp* ksp, const pb_pc_mg_opts* opts);
+int pb_ksp_pc_mg_get_opts(const pb_ksp* ksp, pb_pc_mg_opts* opts);
+/* pb_solve with these settings (mg may be NULL: the defaults) */
+int pb_solve_mg(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_pc_mg_opts* mg,
+                const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
+                int64_t history_cap);
 /* The bounds the next PB_KSP_CHEBYSHEV solve uses (PB_ERR_STATE on a KSP of another type);
  * *estimated = 0 for the caller's own. Without given bounds this runs the estimate if it has not
  * run for the operators' current deltas (so it is collective over the ranks):

@@ -40,6 +40,12 @@ class KspChebyshevOpts(C.Structure):
     _fields_ = [("emin", c_d), ("emax", c_d), ("esteig", c_d * 4), ("esteig_steps", C.c_int)]
 
 
+class PcMgOpts(C.Structure):
+    _fields_ = [("levels_ksp_type", C.c_int), ("levels_pc_type", C.c_int),
+                ("levels_ksp_max_it", C.c_int), ("levels_richardson_scale", c_d),
+                ("levels_eigenvalues", c_d * 2), ("levels_esteig", c_d * 4)]
+
+
 class KspResult(C.Structure):
     _fields_ = [("reason", C.c_int), ("its", c_i64), ("rnorm", c_d), ("rnorm0", c_d),
                 ("nhist", c_i64)]
@@ -125,6 +131,12 @@ _SIGS = {
     "pb_solve_chebyshev": [c_p, c_p, C.POINTER(KspOpts), C.POINTER(KspChebyshevOpts), c_p, c_p,
                            C.POINTER(KspResult), P_d, c_i64],
     "pb_ksp_chebyshev_get_eigenvalues": [c_p, P_d, P_d, C.POINTER(C.c_int)],
+    "pb_pc_mg_opts_default": [C.POINTER(PcMgOpts)],
+    "pb_pc_mg_opts_parse": [C.POINTER(PcMgOpts), C.c_int, C.POINTER(C.c_char_p)],
+    "pb_ksp_pc_mg_set_opts": [c_p, C.POINTER(PcMgOpts)],
+    "pb_ksp_pc_mg_get_opts": [c_p, C.POINTER(PcMgOpts)],
+    "pb_solve_mg": [c_p, c_p, C.POINTER(KspOpts), C.POINTER(PcMgOpts), c_p, c_p,
+                    C.POINTER(KspResult), P_d, c_i64],
     "pb_tridiag_extreme_eigenvalues": [C.c_int, P_d, P_d, P_d, P_d],
     "pb_ksp_pc_apply": [c_p, c_p, c_p],
     "pb_ksp_pc_levels": [c_p, C.POINTER(C.c_int)],

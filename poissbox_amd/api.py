@@ -27,6 +27,9 @@ PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
 # chebyshev = the accelerated stationary iteration for a spectrum of M^-1 A in [emin, emax]
 # (-ksp_chebyshev_eigenvalues emin,emax; estimated when not given: KSP.chebyshev_eigenvalues())
 KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV = 0, 1, 2, 3
+# -mg_levels_ksp_type / -mg_levels_pc_type: the level smoother of -pc_type mg (pb_pc_mg_opts)
+MG_LEVELS_RICHARDSON, MG_LEVELS_CHEBYSHEV = 0, 1
+MG_LEVELS_SOR, MG_LEVELS_JACOBI = 0, 1
 
 REASONS = {0: "CONVERGED_ITERATING", 2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL",
            4: "CONVERGED_ITS", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",
@@ -378,7 +381,44 @@ class KspOptions(L.KspOpts):
     """pb_ksp_opts (the same layout: no field added) together with the Chebyshev settings, which
     the C interface keeps in a struct of their own (pb_ksp_chebyshev_opts; `.chebyshev`); KSP()
     sets them after pb_ksp_create. chebyshev_emin / _emax / _esteig / _esteig_steps read and write
-    that struct."""
+    that struct. Likewise the multigrid's level smoother (pb_pc_mg_opts; `.mg`): mg_levels_ksp_type
+    (MG_LEVELS_RICHARDSON | _CHEBYSHEV), mg_levels_pc_type (MG_LEVELS_SOR | _JACOBI),
+    mg_levels_ksp_max_it, mg_levels_richardson_scale, mg_levels_eigenvalues, mg_levels_esteig;
+    KSP() sets them on a -pc_type mg KSP once one of them was touched or parsed."""
+
+    def _mg(self):
+        if "mg" not in self.__dict__:
+            m = L.PcMgOpts()
+            L.call("pb_pc_mg_opts_default", C.byref(m))
+            self.__dict__["mg"] = m
+        return self.__dict__["mg"]
+
+    mg = property(_mg)
+    mg_levels_ksp_type = property(lambda s: s._mg().levels_ksp_type,
+                                  lambda s, v: setattr(s._mg(), "levels_ksp_type", v))
+    mg_levels_pc_type = property(lambda s: s._mg().levels_pc_type,
+                                 lambda s, v: setattr(s._mg(), "levels_pc_type", v))
+    mg_levels_ksp_max_it = property(lambda s: s._mg().levels_ksp_max_it,
+                                    lambda s, v: setattr(s._mg(), "levels_ksp_max_it", v))
+    mg_levels_richardson_scale = property(
+        lambda s: s._mg().levels_richardson_scale,
+        lambda s, v: setattr(s._mg(), "levels_richardson_scale", v))
+
+    @property
+    def mg_levels_eigenvalues(self):
+        return self._mg().levels_eigenvalues
+
+    @mg_levels_eigenvalues.setter
+    def mg_levels_eigenvalues(self, v):
+        self._mg().levels_eigenvalues = (C.c_double * 2)(*v)
+
+    @property
+    def mg_levels_esteig(self):
+        return self._mg().levels_esteig
+
+    @mg_levels_esteig.setter
+    def mg_levels_esteig(self, v):
+        self._mg().levels_esteig = (C.c_double * 4)(*v)
 
     def _cheb(self):
         if "chebyshev" not in self.__dict__:
@@ -409,9 +449,25 @@ def ksp_options(argv=(), **kw):
         arr = (C.c_char_p * len(argv))(*[str(a).encode() for a in argv])
         L.call("pb_ksp_opts_parse", C.byref(o), len(argv), arr)
         L.call("pb_ksp_chebyshev_opts_parse", C.byref(o.chebyshev), len(argv), arr)
+        if any(str(a).startswith("-mg_") for a in argv):
+            L.call("pb_pc_mg_opts_parse", C.byref(o.mg), len(argv), arr)
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def pc_mg_options(argv=(), **kw):
+    """pb_pc_mg_opts: the defaults, then -mg_levels_* options from argv, then fields by keyword."""
+    m = L.PcMgOpts()
+    L.call("pb_pc_mg_opts_default", C.byref(m))
+    if argv:
+        arr = (C.c_char_p * len(argv))(*[str(a).encode() for a in argv])
+        L.call("pb_pc_mg_opts_parse", C.byref(m), len(argv), arr)
+    for k, v in kw.items():
+        if k in ("levels_eigenvalues", "levels_esteig"):
+            v = (C.c_double * len(v))(*v)
+        setattr(m, k, v)
+    return m
 
 
 def tridiag_extreme_eigenvalues(diag, off=()):
@@ -440,6 +496,22 @@ class KSP:
             except L.PbError:
                 self.destroy()
                 raise
+        # a KSP whose options never named the level smoother is given none (the default path)
+        if self.opts.pc_type == PC_MG and "mg" in getattr(self.opts, "__dict__", {}):
+            try:
+                L.call("pb_ksp_pc_mg_set_opts", h, C.byref(self.opts.mg))
+            except L.PbError:
+                self.destroy()
+                raise
+
+    def pc_mg_set_opts(self, mg):
+        """pb_ksp_pc_mg_set_opts: mg is a PcMgOpts (pc_mg_options())."""
+        L.call("pb_ksp_pc_mg_set_opts", self.h, C.byref(mg))
+
+    def pc_mg_get_opts(self):
+        m = L.PcMgOpts()
+        L.call("pb_ksp_pc_mg_get_opts", self.h, C.byref(m))
+        return m
 
     def solve(self, b, x):
         """Returns (reason, its, history): the res.nhist logged norms (its + 1 of them, its

@@ -303,6 +303,13 @@ int launch_presmooth_residual(pb_grid* g, const Star& s, const double* b, double
                               double omega, const int* skip);
 int launch_mg_residual(pb_grid* g, const Star& s, const double* x, const double* b,
                        const StencilPlanes& gp, double* res, const int* skip);
+// one step of a Jacobi-type level smoother with its residual in one pass (one rank, wrap planes):
+// y_out = omega ((y - yp) + scale ((1 / cc) r)) + yp formed on load, r_out = b - A y_out.
+// yp == nullptr: y_out = omega (y + scale ((1 / cc) r)); y == nullptr too (zero start, r = b):
+// y_out = omega (scale ((1 / cc) b)). y_out and r_out are other buffers than y, yp and r
+int launch_mg_poly(pb_grid* g, const Star& s, const double* y, const double* yp, const double* r,
+                   const double* b, double scale, double omega, double* y_out, double* r_out,
+                   const int* skip);
 
 // CG state (device resident; all scalars computed on device, host only polls `done`)
 // Deferred solution update (defer_x = D in {0, 2, 4}): x += sum of alpha_m p_m over D
@@ -652,6 +659,15 @@ int mg_create(pb_grid* g, const double deltas[3], int pc_type, int levels_req, i
 int mg_apply(Mg* mg, const double* r, double* z, const int* skip = nullptr,
              const CgState* sums_st = nullptr, int* nparts = nullptr);
 int mg_levels(const Mg* mg);
+// the level smoother (pb_pc_mg_opts, checked by the caller): ksp PB_MG_LEVELS_RICHARDSON |
+// _CHEBYSHEV, pc PB_MG_LEVELS_SOR | _JACOBI, nu sweeps / steps per leg, Richardson's scale,
+// Chebyshev's bounds. The defaults (richardson, sor, 1) keep mg_apply's fused V(1,1) path; the
+// Jacobi-type smoothers allocate their extra level arrays here
+struct MgSmoother {
+  int ksp = 0, pc = 0, nu = 1;
+  double rich_scale = 1.0, emin = 0.0, emax = 0.0;
+};
+int mg_set_smoother(Mg* mg, const MgSmoother& sm);
 void mg_destroy(Mg* mg);
 // deterministic level count for a global grid split over nranks z-slabs (every rank agrees)
 int mg_plan_levels(const int64_t n[3], int nranks, int levels_req);

@@ -20,6 +20,11 @@
 //
 // The arithmetic order of every kernel is restated in oracle/pb_oracle.c (pbo_mg_apply), which
 // the tests compare bit for bit.
+//
+// Selectable level smoothers (pb_pc_mg_opts, -mg_levels_*): nu sweeps per leg, and damped Jacobi or
+// Chebyshev over Jacobi instead of SOR (mg_apply_levels at the end of this file; restated in
+// tests/mg_smoothers_restatement.py). The default -- richardson + sor, one sweep -- is mg_apply's
+// fused path above, unchanged.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -45,6 +50,12 @@ struct MgLevel {
   // fused post-smoothing (one rank, large levels): the pre-smoothed x, kept apart from x so that
   // the prolongation + both half-sweeps can read it and write x in one pass
   double* xs = nullptr;
+  // Jacobi-type smoothers (mg_set_smoother): two more iterate buffers and one more residual
+  // buffer -- a step forms y_new at a point's neighbours from y, y_prev and r there, so it writes
+  // to buffers it does not read; x, t1, t2 and res, r2 rotate
+  double* t1 = nullptr;
+  double* t2 = nullptr;
+  double* r2 = nullptr;
   MgGeo geo() const {
     return MgGeo{(int)g->n[0], (int)g->n[1], (int)g->nzl, g->plane, g->nlocal, g->k0};
   }
@@ -77,6 +88,13 @@ struct Mg {
   std::vector<double*> ax, ab, ares;
   double* agg_send = nullptr;              // P copies of this rank's level-La slab
   std::vector<int64_t> agg_sc, agg_rc;     // all-to-all counts (send: own slab; recv: rank q's)
+  // the level smoother (pb_pc_mg_opts). custom(): anything but the default richardson + sor with
+  // one sweep per leg -- runs mg_apply_levels (per-level launches; no fused SOR passes, no tail,
+  // no agglomeration)
+  MgSmoother sm;
+  bool poly() const { return sm.pc == PB_MG_LEVELS_JACOBI; }
+  bool custom() const { return poly() || sm.nu > 1; }
+  double* pmem = nullptr;  // the levels' t1, t2, r2
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -470,6 +488,111 @@ __global__ __launch_bounds__(256) void mg_prolong_z_kernel(MgGeo F, const double
 }
 
 // ---------------------------------------------------------------------------------------------
+// Jacobi-type level smoothers (-mg_levels_pc_type jacobi under richardson or chebyshev). One step:
+//   y_new = omega ((y - yp) + scale (dinv r)) + yp,  dinv = 1 / cc,
+// every operation rounded, in PolyLoad's order (pb_stencil.hip), so the engine pass, the pair
+// kernel and the vector kernel give the same bits. N = 3: y, yp, r; N = 2: y, r (yp = 0 or
+// Richardson); N = 1: the zero start, from b alone.
+// ---------------------------------------------------------------------------------------------
+struct PolyArgs {
+  const double* a0;  // N = 1: b; else y
+  const double* a1;  // N = 2: r; N = 3: yp
+  const double* a2;  // N = 3: r
+  double scale, omega, dinv;
+};
+template <int N>
+__device__ __forceinline__ double poly_value(const PolyArgs& A, double v0, double v1, double v2) {
+  if constexpr (N == 1) {
+    const double z = A.dinv * v0;
+    const double u = A.scale * z;
+    return A.omega * u;
+  } else if constexpr (N == 2) {
+    const double z = A.dinv * v1;
+    const double u = A.scale * z;
+    const double t = v0 + u;
+    return A.omega * t;
+  } else {
+    const double z = A.dinv * v2;
+    double t = v0 - v1;
+    const double u = A.scale * z;
+    t = t + u;
+    t = A.omega * t;
+    return t + v1;
+  }
+}
+template <int N>
+__device__ __forceinline__ double poly_at(const PolyArgs& A, int64_t id) {
+  return poly_value<N>(A, A.a0[id], N >= 2 ? A.a1[id] : 0.0, N >= 3 ? A.a2[id] : 0.0);
+}
+template <int N>
+__device__ __forceinline__ dv2 poly_pair(const PolyArgs& A, int64_t id) {
+  const dv2 v0 = *(const dv2*)(A.a0 + id);
+  dv2 v1 = v0, v2 = v0;
+  if constexpr (N >= 2) v1 = *(const dv2*)(A.a1 + id);
+  if constexpr (N >= 3) v2 = *(const dv2*)(A.a2 + id);
+  dv2 o;
+  o.x = poly_value<N>(A, v0.x, v1.x, v2.x);
+  o.y = poly_value<N>(A, v0.y, v1.y, v2.y);
+  return o;
+}
+
+// the vector kernel: y_out = the step's y_new (the unfused form, and a post-smoothing's last
+// step, whose residual nobody reads). Elementwise: y_out may be one of the inputs.
+template <int N>
+__global__ __launch_bounds__(256) void mg_poly_x_kernel(int64_t npairs, PolyArgs A, double* y_out,
+                                                        const int* skip) {
+  if (skip && *skip) return;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    const dv2 o = poly_pair<N>(A, 2 * q);
+    *(dv2*)(y_out + 2 * q) = o;
+  }
+}
+
+// the pair kernel (one rank, small levels): y_new formed at the pair and its neighbours, stored
+// with r_new = b - A y_new (mg_residual_body's sums). y_out, r_out: buffers the step does not read.
+template <int N>
+__global__ __launch_bounds__(256) void mg_poly_kernel(MgGeo G, PolyArgs A,
+                                                      const double* __restrict__ b, Star s,
+                                                      double* __restrict__ y_out,
+                                                      double* __restrict__ r_out, const int* skip) {
+  if (skip && *skip) return;
+  const int64_t npairs = G.nlocal >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    const PairPos P = pair_pos(G, q);
+    const int64_t row = P.idx - P.i0;
+    const dv2 xc = poly_pair<N>(A, P.idx);
+    const dv2 bc = *(const dv2*)(b + P.idx);
+    const dv2 zm = poly_pair<N>(A, P.idx + (int64_t)(wrapm(P.k - 1, G.nzl) - P.k) * G.plane);
+    const dv2 zp = poly_pair<N>(A, P.idx + (int64_t)(wrapm(P.k + 1, G.nzl) - P.k) * G.plane);
+    const dv2 ym = poly_pair<N>(A, P.idx + (int64_t)(wrapm(P.j - 1, G.ny) - P.j) * G.nx);
+    const dv2 yp = poly_pair<N>(A, P.idx + (int64_t)(wrapm(P.j + 1, G.ny) - P.j) * G.nx);
+    const double xl = poly_at<N>(A, row + wrapm(P.i0 - 1, G.nx));
+    const double xr = poly_at<N>(A, row + wrapm(P.i0 + 2, G.nx));
+    double a0 = s.cz * zm.x;
+    a0 = a0 + s.cy * ym.x;
+    a0 = a0 + s.cx * xl;
+    a0 = a0 + s.cc * xc.x;
+    a0 = a0 + s.cx * xc.y;
+    a0 = a0 + s.cy * yp.x;
+    a0 = a0 + s.cz * zp.x;
+    double a1 = s.cz * zm.y;
+    a1 = a1 + s.cy * ym.y;
+    a1 = a1 + s.cx * xc.x;
+    a1 = a1 + s.cc * xc.y;
+    a1 = a1 + s.cx * xr;
+    a1 = a1 + s.cy * yp.y;
+    a1 = a1 + s.cz * zp.y;
+    dv2 o;
+    o.x = bc.x - a0;
+    o.y = bc.y - a1;
+    *(dv2*)(r_out + P.idx) = o;
+    *(dv2*)(y_out + P.idx) = xc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The coarse tail of the V-cycle in ONE launch (one rank): every level of at most
 // PB_MG_TAIL_MAX points (16^3 at 512^3: the 16^3, 8^3 and 4^3 levels) -- down-legs, the coarsest
 // level's sweeps and the up-legs -- run by one workgroup, step after step with a barrier between
@@ -659,6 +782,7 @@ void mg_destroy(Mg* mg) {
     if (L.own) pb_grid_destroy(L.g);
   if (mg->mem) (void)hipFree(mg->mem);
   if (mg->agg) (void)hipFree(mg->agg);
+  if (mg->pmem) (void)hipFree(mg->pmem);
   delete mg;
 }
 
@@ -814,9 +938,12 @@ static bool post_fused(const Mg* mg, int l) {
   return C.g->n[0] * C.g->n[1] >= mg->restrict_z_min_cols;
 }
 
+static int mg_apply_levels(Mg* mg, const double* r, double* z, const int* skip);
+
 int mg_apply(Mg* mg, const double* r, double* z, const int* skip, const CgState* sums_st,
              int* nparts) {
   if (nparts) *nparts = 0;
+  if (mg->custom()) return mg_apply_levels(mg, r, z, skip);  // (the caller takes CG's sums)
   ScopedTimer tm(mg->ctx, "mg_apply");
   mg->skip = skip;
   mg->engine_min_plane = tune("mg_engine_min_plane", mg_engine_min_plane_default(mg->ctx));
@@ -977,6 +1104,215 @@ int mg_apply(Mg* mg, const double* r, double* z, const int* skip, const CgState*
     } else {
       PB_TRY(smooth(mg, F, 1, 0));
       PB_TRY(smooth(mg, F, 0, 0, l == 0 ? sums_st : nullptr, nparts));
+    }
+  }
+  return PB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Selectable level smoothers (pb_pc_mg_opts): the V-cycle by per-level launches
+// ---------------------------------------------------------------------------------------------
+int mg_set_smoother(Mg* mg, const MgSmoother& sm) {
+  const int L = (int)mg->lv.size();
+  if (sm.pc == PB_MG_LEVELS_JACOBI && !mg->pmem && L > 1) {
+    int64_t total = 0;
+    for (int l = 0; l < L - 1; ++l) total += 3 * mg->lv[l].g->nlocal;
+    if (hipMalloc(&mg->pmem, (size_t)total * sizeof(double)) != hipSuccess)
+      return set_error(PB_ERR_ALLOC, "multigrid level smoother: out of device memory");
+    double* p = mg->pmem;
+    for (int l = 0; l < L - 1; ++l) {
+      MgLevel& lv = mg->lv[l];
+      lv.t1 = p;
+      lv.t2 = p + lv.g->nlocal;
+      lv.r2 = p + 2 * lv.g->nlocal;
+      p += 3 * lv.g->nlocal;
+    }
+  }
+  mg->sm = sm;
+  return PB_OK;
+}
+
+// res = b - A x of level F (engine on large levels, the pair kernel below)
+static int level_residual(Mg* mg, MgLevel& F, const double* x, double* res) {
+  const double *lo, *hi;
+  PB_TRY(ghosts(F, x, &lo, &hi));
+  if (F.g->plane >= mg->engine_min_plane)
+    return launch_mg_residual(F.g, F.s, x, F.b, StencilPlanes{lo, hi}, res, mg->skip);
+  const MgGeo G = F.geo();
+  hipLaunchKernelGGL(mg_residual_kernel, dim3(mg_blocks(mg->ctx, G.nlocal / 2)), dim3(256), 0,
+                     mg->ctx->stream, G, x, (const double*)F.b, lo, hi, F.s, res, mg->skip);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+static int level_restrict(Mg* mg, MgLevel& F, const double* res, MgLevel& Cl) {
+  const double *lo, *hi;
+  PB_TRY(ghosts(F, res, &lo, &hi));
+  const MgGeo G = F.geo(), CG = Cl.geo();
+  const int64_t cols = (int64_t)CG.nx * CG.ny;
+  if (cols >= mg->restrict_z_min_cols) {
+    int64_t nchunk = 1;
+    const int kc = transfer_chunk(mg->ctx, cols, CG.nzl, &nchunk);
+    hipLaunchKernelGGL(mg_restrict_z_kernel, dim3(mg_blocks(mg->ctx, cols * nchunk)), dim3(256), 0,
+                       mg->ctx->stream, G, res, lo, hi, CG, kc, Cl.b, mg->skip);
+  } else {
+    hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_blocks(mg->ctx, CG.nlocal)), dim3(256), 0,
+                       mg->ctx->stream, G, res, lo, hi, CG, Cl.b, mg->skip);
+  }
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+// xf += P xc, in place
+static int level_prolong(Mg* mg, MgLevel& F, double* xf, MgLevel& Cl) {
+  const double *lo, *hi;
+  PB_TRY(ghosts(Cl, Cl.x, &lo, &hi));
+  const MgGeo G = F.geo(), CG = Cl.geo();
+  const int64_t cols = (int64_t)CG.nx * CG.ny;
+  if (cols >= mg->restrict_z_min_cols) {
+    int64_t nchunk = 1;
+    const int kc = transfer_chunk(mg->ctx, cols, CG.nzl, &nchunk);
+    hipLaunchKernelGGL(mg_prolong_z_kernel, dim3(mg_blocks(mg->ctx, cols * nchunk)), dim3(256), 0,
+                       mg->ctx->stream, G, (const double*)xf, xf, CG, kc, (const double*)Cl.x, lo,
+                       hi, mg->skip);
+  } else {
+    hipLaunchKernelGGL(mg_prolong_cell_kernel, dim3(mg_blocks(mg->ctx, CG.nlocal)), dim3(256), 0,
+                       mg->ctx->stream, G, xf, CG, (const double*)Cl.x, lo, hi, mg->skip);
+  }
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
+
+// One step of a Jacobi-type smoother on level F. y == nullptr: the zero start (r = b);
+// yp == nullptr: no y_prev term. r_out == nullptr: the iterate alone (y_out may alias an input).
+// Fused (one rank, tuning mg_poly_fused = 1): the engine pass on large levels, the pair kernel
+// below; else the vector kernel, a ghost exchange of y_out and the residual pass -- the same
+// expressions, so the same bits, and what a decomposed grid runs.
+static int poly_step(Mg* mg, MgLevel& F, const double* y, const double* yp, const double* r,
+                     double scale, double omega, double* y_out, double* r_out) {
+  pb_ctx* ctx = mg->ctx;
+  const MgGeo G = F.geo();
+  const int n = !y ? 1 : (!yp ? 2 : 3);
+  const double dinv = 1.0 / F.s.cc;
+  const PolyArgs A = n == 1 ? PolyArgs{F.b, nullptr, nullptr, scale, omega, dinv}
+                   : n == 2 ? PolyArgs{y, r, nullptr, scale, omega, dinv}
+                            : PolyArgs{y, yp, r, scale, omega, dinv};
+  const dim3 grid(mg_blocks(ctx, G.nlocal / 2)), block(256);
+  const bool fused = r_out && !ctx->split && tune("mg_poly_fused", 1) != 0;
+  if (fused && F.g->plane >= mg->engine_min_plane)
+    return launch_mg_poly(F.g, F.s, y, yp, r, F.b, scale, omega, y_out, r_out, mg->skip);
+  if (fused) {
+    const double* b = F.b;
+    if (n == 1)
+      hipLaunchKernelGGL(mg_poly_kernel<1>, grid, block, 0, ctx->stream, G, A, b, F.s, y_out, r_out,
+                         mg->skip);
+    else if (n == 2)
+      hipLaunchKernelGGL(mg_poly_kernel<2>, grid, block, 0, ctx->stream, G, A, b, F.s, y_out, r_out,
+                         mg->skip);
+    else
+      hipLaunchKernelGGL(mg_poly_kernel<3>, grid, block, 0, ctx->stream, G, A, b, F.s, y_out, r_out,
+                         mg->skip);
+    PB_HIP(hipGetLastError());
+    return PB_OK;
+  }
+  const int64_t npairs = G.nlocal / 2;
+  if (n == 1)
+    hipLaunchKernelGGL(mg_poly_x_kernel<1>, grid, block, 0, ctx->stream, npairs, A, y_out, mg->skip);
+  else if (n == 2)
+    hipLaunchKernelGGL(mg_poly_x_kernel<2>, grid, block, 0, ctx->stream, npairs, A, y_out, mg->skip);
+  else
+    hipLaunchKernelGGL(mg_poly_x_kernel<3>, grid, block, 0, ctx->stream, npairs, A, y_out, mg->skip);
+  PB_HIP(hipGetLastError());
+  return r_out ? level_residual(mg, F, y_out, r_out) : PB_OK;
+}
+
+// nu steps of the Jacobi-type smoother on level F. pre: from zero, every step with its residual
+// (the last one's is the V-cycle's); *ycur, *rcur = where the iterate and its residual ended up.
+// post: from *ycur (its residual taken first), the last step stores no residual and writes F.x.
+static int poly_smooth(Mg* mg, MgLevel& F, bool pre, double** ycur, double** rcur) {
+  const MgSmoother& sm = mg->sm;
+  const bool cheb = sm.ksp == PB_MG_LEVELS_CHEBYSHEV;
+  double scale = sm.rich_scale, mu = 0.0, omegaprod = 0.0, rho = 0.0;
+  if (cheb) {  // KSPSolve_Chebyshev's coefficients, restarted at every smoothing call
+    scale = 2.0 / (sm.emax + sm.emin);
+    const double alpha = 1.0 - scale * sm.emin;
+    mu = 1.0 / alpha;
+    omegaprod = 2.0 / alpha;
+    rho = 1.0 / mu;
+  }
+  double* const ybuf[3] = {F.x, F.t1, F.t2};
+  auto pick = [&](const double* a, const double* c) {
+    for (double* q : ybuf)
+      if (q != a && q != c) return q;
+    return (double*)nullptr;
+  };
+  const double* y = nullptr;
+  const double* yp = nullptr;
+  const double* r = nullptr;
+  if (!pre) {
+    y = *ycur;
+    PB_TRY(level_residual(mg, F, y, F.res));
+    r = F.res;
+  }
+  for (int i = 0; i < sm.nu; ++i) {
+    double omega = 1.0;
+    if (cheb && i >= 1) {
+      rho = 1.0 / (2.0 * mu - rho);
+      omega = omegaprod * rho;
+    }
+    // y_prev enters from Chebyshev's second step on; after a zero start it is 0 in step 1
+    const double* ypa = cheb && i >= 1 && !(pre && i == 1) ? yp : nullptr;
+    const bool last = !pre && i == sm.nu - 1;
+    double* yo = last ? F.x : pick(y, yp);
+    double* ro = last ? nullptr : (r == F.res ? F.r2 : F.res);
+    PB_TRY(poly_step(mg, F, y, ypa, r, scale, omega, yo, ro));
+    yp = y;
+    y = yo;
+    r = ro;
+  }
+  *ycur = const_cast<double*>(y);
+  *rcur = const_cast<double*>(r);
+  return PB_OK;
+}
+
+static int mg_apply_levels(Mg* mg, const double* r, double* z, const int* skip) {
+  ScopedTimer tm(mg->ctx, "mg_apply");
+  mg->skip = skip;
+  mg->engine_min_plane = tune("mg_engine_min_plane", mg_engine_min_plane_default(mg->ctx));
+  mg->restrict_z_min_cols = tune("mg_restrict_z_min_cols", 4096);
+  const int L = (int)mg->lv.size();
+  const int nu = mg->sm.nu;
+  mg->lv[0].b = const_cast<double*>(r);
+  mg->lv[0].x = z;
+  std::vector<double*> cur(L, nullptr);  // where level l's pre-smoothed iterate lives
+  for (int l = 0; l < L - 1; ++l) {  // down: pre-smooth, residual, restrict
+    MgLevel& F = mg->lv[l];
+    double* res = F.res;
+    if (mg->poly()) {
+      PB_TRY(poly_smooth(mg, F, true, &cur[l], &res));
+    } else {  // nu x (red, black), the first pair from zero
+      PB_TRY(smooth(mg, F, 0, 1));
+      for (int i = 1; i < nu; ++i) {
+        PB_TRY(smooth(mg, F, 0, 0));
+        PB_TRY(smooth(mg, F, 1, 0));
+      }
+      cur[l] = F.x;
+      PB_TRY(level_residual(mg, F, F.x, res));
+    }
+    PB_TRY(level_restrict(mg, F, res, mg->lv[l + 1]));
+  }
+  PB_TRY(coarse_solve(mg, mg->lv[L - 1], nullptr, nullptr));
+  for (int l = L - 2; l >= 0; --l) {  // up: prolongate + correct, post-smooth
+    MgLevel& F = mg->lv[l];
+    PB_TRY(level_prolong(mg, F, cur[l], mg->lv[l + 1]));
+    if (mg->poly()) {
+      double* res = nullptr;
+      PB_TRY(poly_smooth(mg, F, false, &cur[l], &res));
+    } else {  // nu x (black, red): the pre-smoothing mirrored
+      for (int i = 0; i < nu; ++i) {
+        PB_TRY(smooth(mg, F, 1, 0));
+        PB_TRY(smooth(mg, F, 0, 0));
+      }
     }
   }
   return PB_OK;

@@ -68,6 +68,7 @@ struct pb_ksp {
     return i == 0 && !rich_guess ? b->d : ((i & 1) ? r2 : r);
   }
   pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
+  pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
   int fold_nparts_b = 0;     // partial-sum blocks of the last folded pass B
   bool stored_z() const { return mg || fft; }  // PCs whose z = M^-1 r is stored (not Jacobi)
@@ -269,6 +270,130 @@ int pb_ksp_chebyshev_opts_default(pb_ksp_chebyshev_opts* o) {
   for (int i = 0; i < 4; ++i) o->esteig[i] = tr[i];
   o->esteig_steps = 10;
   return PB_OK;
+}
+
+static bool parse_real_list(const char* v, int n, double* out);
+
+int pb_pc_mg_opts_default(pb_pc_mg_opts* o) {
+  PB_CHECK_ARG(o, "opts is NULL");
+  o->levels_ksp_type = PB_MG_LEVELS_RICHARDSON;
+  o->levels_pc_type = PB_MG_LEVELS_SOR;
+  o->levels_ksp_max_it = 1;
+  o->levels_richardson_scale = 1.0;
+  o->levels_eigenvalues[0] = o->levels_eigenvalues[1] = 0.0;  // 0, 0: the transform of (0, 2)
+  const double tr[4] = {0.0, 0.1, 0.0, 1.1};
+  for (int i = 0; i < 4; ++i) o->levels_esteig[i] = tr[i];
+  return PB_OK;
+}
+
+// the level smoother's Chebyshev interval: D^-1 A is positive semi-definite
+static int check_mg_pair(double emin, double emax, const char* what) {
+  if (!std::isfinite(emin) || !std::isfinite(emax) || !(emin > 0.0) || !(emax > emin))
+    return set_error(PB_ERR_ARG, "%s: emin %g, emax %g are no finite bounds with 0 < emin < emax",
+                     what, emin, emax);
+  return PB_OK;
+}
+
+// the bounds the level smoother runs with: the caller's, or the esteig transform of D^-1 A's
+// exact extremes (0, 2) on every level
+static void mg_levels_bounds(const pb_pc_mg_opts* o, double* emin, double* emax) {
+  if (o->levels_eigenvalues[0] != 0.0 || o->levels_eigenvalues[1] != 0.0) {
+    *emin = o->levels_eigenvalues[0];
+    *emax = o->levels_eigenvalues[1];
+    return;
+  }
+  const double lo = 0.0, hi = 2.0;
+  *emin = o->levels_esteig[0] * lo + o->levels_esteig[1] * hi;
+  *emax = o->levels_esteig[2] * lo + o->levels_esteig[3] * hi;
+}
+
+static int check_mg_opts(const pb_pc_mg_opts* o) {
+  const int kt = o->levels_ksp_type, pt = o->levels_pc_type;
+  if (kt != PB_MG_LEVELS_RICHARDSON && kt != PB_MG_LEVELS_CHEBYSHEV)
+    return set_error(PB_ERR_ARG, "unknown mg levels_ksp_type %d", kt);
+  if (pt != PB_MG_LEVELS_SOR && pt != PB_MG_LEVELS_JACOBI)
+    return set_error(PB_ERR_ARG, "unknown mg levels_pc_type %d", pt);
+  if (o->levels_ksp_max_it < 1 || o->levels_ksp_max_it > 8)
+    return set_error(PB_ERR_ARG, "-mg_levels_ksp_max_it %d outside 1..8", o->levels_ksp_max_it);
+  if (!std::isfinite(o->levels_richardson_scale) || !(o->levels_richardson_scale > 0.0))
+    return set_error(PB_ERR_ARG, "-mg_levels_ksp_richardson_scale %g is not finite and > 0",
+                     o->levels_richardson_scale);
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(o->levels_esteig[i]))
+      return set_error(PB_ERR_ARG, "mg levels_esteig[%d] is not finite", i);
+  if (o->levels_eigenvalues[0] != 0.0 || o->levels_eigenvalues[1] != 0.0)
+    PB_TRY(check_mg_pair(o->levels_eigenvalues[0], o->levels_eigenvalues[1],
+                         "-mg_levels_ksp_chebyshev_eigenvalues"));
+  if (kt == PB_MG_LEVELS_CHEBYSHEV) {
+    if (pt == PB_MG_LEVELS_SOR)
+      return set_error(PB_ERR_UNSUPPORTED,
+                       "-mg_levels_ksp_type chebyshev with -mg_levels_pc_type sor: the polynomial "
+                       "smoother runs over jacobi only");
+    double emin, emax;
+    mg_levels_bounds(o, &emin, &emax);
+    PB_TRY(check_mg_pair(emin, emax, "-mg_levels_ksp_chebyshev_esteig transform of (0, 2)"));
+  }
+  if (pt == PB_MG_LEVELS_SOR && o->levels_richardson_scale != 1.0)
+    return set_error(PB_ERR_UNSUPPORTED,
+                     "-mg_levels_ksp_richardson_scale %g with -mg_levels_pc_type sor: only 1 "
+                     "(the relaxation factor is -pc_sor_omega)", o->levels_richardson_scale);
+  return PB_OK;
+}
+
+int pb_pc_mg_opts_parse(pb_pc_mg_opts* o, int argc, const char* const* argv) {
+  PB_CHECK_ARG(o, "opts is NULL");
+  for (int i = 0; i < argc; ++i) {
+    const char* a = argv[i];
+    const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+    if (!a || strncmp(a, "-mg_", 4) || !v) continue;
+    if (!strcmp(a, "-mg_levels_ksp_type")) {
+      if (!strcmp(v, "richardson")) o->levels_ksp_type = PB_MG_LEVELS_RICHARDSON;
+      else if (!strcmp(v, "chebyshev")) o->levels_ksp_type = PB_MG_LEVELS_CHEBYSHEV;
+      else
+        return set_error(PB_ERR_UNSUPPORTED, "-mg_levels_ksp_type %s: only richardson, chebyshev",
+                         v);
+      ++i;
+    } else if (!strcmp(a, "-mg_levels_pc_type")) {
+      if (!strcmp(v, "sor")) o->levels_pc_type = PB_MG_LEVELS_SOR;
+      else if (!strcmp(v, "jacobi")) o->levels_pc_type = PB_MG_LEVELS_JACOBI;
+      else return set_error(PB_ERR_UNSUPPORTED, "-mg_levels_pc_type %s: only sor, jacobi", v);
+      ++i;
+    } else if (!strcmp(a, "-mg_levels_ksp_max_it")) {
+      const int n = atoi(v);
+      if (n < 1 || n > 8)
+        return set_error(PB_ERR_ARG, "-mg_levels_ksp_max_it %s: outside 1..8", v);
+      o->levels_ksp_max_it = n;
+      ++i;
+    } else if (!strcmp(a, "-mg_levels_ksp_richardson_scale")) {
+      const double s = atof(v);
+      if (!std::isfinite(s) || !(s > 0.0))
+        return set_error(PB_ERR_ARG, "-mg_levels_ksp_richardson_scale %s: not finite and > 0", v);
+      o->levels_richardson_scale = s;
+      ++i;
+    } else if (!strcmp(a, "-mg_levels_ksp_chebyshev_eigenvalues")) {
+      double e[2];
+      if (!parse_real_list(v, 2, e))
+        return set_error(PB_ERR_ARG, "-mg_levels_ksp_chebyshev_eigenvalues %s: expected emin,emax",
+                         v);
+      PB_TRY(check_mg_pair(e[0], e[1], "-mg_levels_ksp_chebyshev_eigenvalues"));
+      o->levels_eigenvalues[0] = e[0];
+      o->levels_eigenvalues[1] = e[1];
+      ++i;
+    } else if (!strcmp(a, "-mg_levels_ksp_chebyshev_esteig")) {
+      double t[4];
+      if (!parse_real_list(v, 4, t))
+        return set_error(PB_ERR_ARG, "-mg_levels_ksp_chebyshev_esteig %s: expected a,b,c,d", v);
+      for (int j = 0; j < 4; ++j) {
+        if (!std::isfinite(t[j]))
+          return set_error(PB_ERR_ARG, "-mg_levels_ksp_chebyshev_esteig %s: not finite", v);
+        o->levels_esteig[j] = t[j];
+      }
+      ++i;
+    } else if (!strcmp(a, "-mg_levels_ksp_rtol") || !strcmp(a, "-mg_coarse_sub_pc_type")) {
+      ++i;  // accepted, no effect: fixed sweep counts, SOR sweeps on the coarsest level
+    }
+  }
+  return check_mg_opts(o);
 }
 
 // Chebyshev's interval: finite, non-zero, of one sign (negative pairs are legal, as in PETSc: A is
@@ -474,6 +599,10 @@ int pb_ksp_opts_parse(pb_ksp_opts* o, int argc, const char* const* argv) {
   pb_ksp_chebyshev_opts co;
   pb_ksp_chebyshev_opts_default(&co);
   PB_TRY(pb_ksp_chebyshev_opts_parse(&co, argc, argv));
+  // likewise the -mg_levels_* options (pb_pc_mg_opts_parse keeps the values)
+  pb_pc_mg_opts mo;
+  pb_pc_mg_opts_default(&mo);
+  PB_TRY(pb_pc_mg_opts_parse(&mo, argc, argv));
   return check_ref_norm_opts(o);
 }
 
@@ -503,6 +632,7 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
       kt != PB_KSP_CHEBYSHEV)
     return fail(set_error(PB_ERR_UNSUPPORTED, "unknown ksp_type %d", kt));
   pb_ksp_chebyshev_opts_default(&k->copts);
+  pb_pc_mg_opts_default(&k->mgopts);
   if (!std::isfinite(k->opts.richardson_scale))
     return fail(set_error(PB_ERR_ARG, "richardson_scale is not finite"));
   if (kt == PB_KSP_PREONLY &&
@@ -1783,6 +1913,32 @@ int pb_ksp_chebyshev_set_opts(pb_ksp* k, const pb_ksp_chebyshev_opts* o) {
   return PB_OK;
 }
 
+int pb_ksp_pc_mg_set_opts(pb_ksp* k, const pb_pc_mg_opts* o) {
+  PB_CHECK_ARG(k && o, "bad args");
+  if (k->opts.pc_type != PB_PC_MG || !k->mg)
+    return set_error(PB_ERR_STATE, "KSP created without -pc_type mg");
+  if (k->begun) return set_error(PB_ERR_STATE, "pb_ksp_pc_mg_set_opts inside a solve");
+  PB_TRY(check_mg_opts(o));
+  MgSmoother sm;
+  sm.ksp = o->levels_ksp_type;
+  sm.pc = o->levels_pc_type;
+  sm.nu = o->levels_ksp_max_it;
+  sm.rich_scale = o->levels_richardson_scale;
+  mg_levels_bounds(o, &sm.emin, &sm.emax);
+  PB_TRY(mg_set_smoother(k->mg, sm));
+  k->mgopts = *o;
+  k->cheb_state = 0;  // an outer Chebyshev's estimate belongs to the old preconditioner
+  return PB_OK;
+}
+
+int pb_ksp_pc_mg_get_opts(const pb_ksp* k, pb_pc_mg_opts* o) {
+  PB_CHECK_ARG(k && o, "bad args");
+  if (k->opts.pc_type != PB_PC_MG || !k->mg)
+    return set_error(PB_ERR_STATE, "KSP created without -pc_type mg");
+  *o = k->mgopts;
+  return PB_OK;
+}
+
 int pb_ksp_chebyshev_get_eigenvalues(pb_ksp* k, double* emin, double* emax, int* estimated) {
   PB_CHECK_ARG(k, "ksp is NULL");
   if (!k->cheb()) return set_error(PB_ERR_STATE, "KSP created without -ksp_type chebyshev");
@@ -1842,9 +1998,24 @@ int pb_solve(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_vec* b, pb_ve
   return pb_solve_chebyshev(A, P, opts, nullptr, b, x, res, history, cap);
 }
 
+static int solve_once(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
+                      const pb_ksp_chebyshev_opts* cheb, const pb_pc_mg_opts* mgo, const pb_vec* b,
+                      pb_vec* x, pb_ksp_result* res, double* history, int64_t cap);
+
 int pb_solve_chebyshev(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
                        const pb_ksp_chebyshev_opts* cheb, const pb_vec* b, pb_vec* x,
                        pb_ksp_result* res, double* history, int64_t cap) {
+  return solve_once(A, P, opts, cheb, nullptr, b, x, res, history, cap);
+}
+
+int pb_solve_mg(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_pc_mg_opts* mgo,
+                const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history, int64_t cap) {
+  return solve_once(A, P, opts, nullptr, mgo, b, x, res, history, cap);
+}
+
+static int solve_once(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
+                      const pb_ksp_chebyshev_opts* cheb, const pb_pc_mg_opts* mgo, const pb_vec* b,
+                      pb_vec* x, pb_ksp_result* res, double* history, int64_t cap) {
   pb_ksp* k = nullptr;
   pb_ksp_opts one;
   if (opts && opts->guess_type == PB_GUESS_FISCHER) {
@@ -1856,6 +2027,7 @@ int pb_solve_chebyshev(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
   }
   PB_TRY(pb_ksp_create(A, P, opts, &k));
   int rc = cheb && k->cheb() ? pb_ksp_chebyshev_set_opts(k, cheb) : PB_OK;
+  if (rc == PB_OK && mgo && k->opts.pc_type == PB_PC_MG) rc = pb_ksp_pc_mg_set_opts(k, mgo);
   if (rc == PB_OK) rc = pb_ksp_solve(k, b, x, res, history, cap);
   const std::string msg = rc != PB_OK ? pb_last_error() : "";
   pb_ksp_destroy(k);

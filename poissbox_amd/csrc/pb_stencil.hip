@@ -430,6 +430,75 @@ struct RichEpi {
   }
 };
 
+// The Jacobi-type level smoothers of the multigrid (-mg_levels_pc_type jacobi under richardson or
+// chebyshev, pb_mg.hip): one smoothing step and its residual in one pass. The field is
+//   y_new = omega ((y - yp) + scale (dinv r)) + yp,
+// formed on load from up to three raw arrays, every operation rounded in this order
+// (mg_poly_kernel in pb_mg.hip is the same expression per pair). scale, omega and dinv = 1 / cc
+// are host-known constants passed by value: no state prologue, no mean shift, no sums.
+//   PolyLoad<3>: y, yp, r  (Chebyshev step i >= 2; 48 B/DoF with b and the two stores)
+//   PolyLoad<2>: y, r      (yp = 0 or Richardson: y - 0 and + 0 are exact, so the same bits)
+//   PolyLoad<1>: b         (the zero start, y = yp = 0 and r = b: neither is read; PolyEpi<true>
+//                           takes b for the residual from the z-queue, 24 B/DoF)
+// PolyEpi stores the centre value y_new and r_new = b - A y_new (reference summation order) to
+// other buffers than the loaders read: neighbouring waves still read y, yp, r around this point.
+template <int N>
+struct PolyLoad {
+  static constexpr int NR = N;
+  static constexpr bool GHOST_RAW = true;
+  const double* __restrict__ a0;  // N = 1: b; else y
+  const double* __restrict__ a1;  // N = 2: r; N = 3: yp
+  const double* __restrict__ a2;  // N = 3: r
+  double scale, omega, dinv;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ const double* src(int a) const {
+    return a == 0 ? a0 : (a == 1 ? a1 : a2);
+  }
+  __device__ __forceinline__ double value(const double* raw) const {
+    if constexpr (N == 1) {
+      const double z = dinv * raw[0];
+      const double u = scale * z;
+      return omega * u;
+    } else if constexpr (N == 2) {
+      const double z = dinv * raw[1];
+      const double u = scale * z;
+      const double t = raw[0] + u;
+      return omega * t;
+    } else {
+      const double z = dinv * raw[2];
+      double t = raw[0] - raw[1];
+      const double u = scale * z;
+      t = t + u;
+      t = omega * t;
+      return t + raw[1];
+    }
+  }
+};
+template <bool QB>
+struct PolyEpi {
+  static constexpr int NS = 0, NE = 1;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true, WIDE8 = true;
+  static constexpr bool PREFETCH = true;
+  // QB (PolyLoad<1>): operand b is the centre plane's raw queue value
+  static constexpr int qop(int) { return QB ? 0 : -1; }
+  double* __restrict__ y_out;
+  double* __restrict__ r_out;
+  const double* __restrict__ b;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ const double* src(int) const { return b; }
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[1][V], double*, int nt) const {
+    double rv[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) rv[e] = op[0][e] - w[e];
+    store_row<V>(r_out, idx, rv, nt);
+    store_row<V>(y_out, idx, c, nt);
+  }
+};
+
 // Epi::qop(a) (optional): operand a is raw z-queue array qop(a) of the centre plane (-1: loaded)
 template <class E, class = void>
 struct HasQop {
@@ -1042,6 +1111,24 @@ int launch_mg_residual(pb_grid* g, const Star& s, const double* x, const double*
                        const StencilPlanes& gp, double* res, const int* skip) {
   ScopedTimer tm(g->ctx, "mg_residual");
   return launch_any(g, s, PlainLoad{x}, gp, ResidEpi{res, b}, skip);
+}
+
+int launch_mg_poly(pb_grid* g, const Star& s, const double* y, const double* yp, const double* r,
+                   const double* b, double scale, double omega, double* y_out, double* r_out,
+                   const int* skip) {
+  ScopedTimer tm(g->ctx, "mg_poly");
+  if (g->ctx->split)  // the update-on-load form reads y, yp and r on the wrap planes in place
+    return set_error(PB_ERR_STATE, "launch_mg_poly on a decomposed grid");
+  const StencilPlanes gp{nullptr, nullptr, true};
+  const double dinv = 1.0 / s.cc;
+  if (!y)
+    return launch_any(g, s, PolyLoad<1>{b, nullptr, nullptr, scale, omega, dinv}, gp,
+                      PolyEpi<true>{y_out, r_out, b}, skip);
+  if (!yp)
+    return launch_any(g, s, PolyLoad<2>{y, r, nullptr, scale, omega, dinv}, gp,
+                      PolyEpi<false>{y_out, r_out, b}, skip);
+  return launch_any(g, s, PolyLoad<3>{y, yp, r, scale, omega, dinv}, gp,
+                    PolyEpi<false>{y_out, r_out, b}, skip);
 }
 
 // ---------------------------------------------------------------------------------------------

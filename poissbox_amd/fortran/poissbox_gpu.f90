@@ -72,6 +72,16 @@ module poissbox_gpu
      integer(c_int) :: esteig_steps          ! -ksp_chebyshev_esteig_steps (10)
   end type pb_ksp_chebyshev_opts
 
+  !! -pc_type mg's level smoother (-mg_levels_*; a struct of its own: pb_ksp_pc_mg_set_opts)
+  type, bind(C), public :: pb_pc_mg_opts
+     integer(c_int) :: levels_ksp_type          ! richardson (0) | chebyshev (1)
+     integer(c_int) :: levels_pc_type           ! sor (0) | jacobi (1)
+     integer(c_int) :: levels_ksp_max_it        ! sweeps / steps per leg, 1..8 (1)
+     real(c_double) :: levels_richardson_scale  ! (1.0)
+     real(c_double) :: levels_eigenvalues(2)    ! emin, emax (0, 0: the transform of (0, 2))
+     real(c_double) :: levels_esteig(4)         ! a, b, c, d (0, 0.1, 0, 1.1)
+  end type pb_pc_mg_opts
+
   type, bind(C), public :: pb_ksp_result
      integer(c_int) :: reason
      integer(c_int64_t) :: its
@@ -102,6 +112,9 @@ module poissbox_gpu
   public :: c_pb_ksp_chebyshev_get_eigenvalues, c_pb_tridiag_extreme_eigenvalues
   public :: c_pb_ksp_chebyshev_opts_default, c_pb_ksp_chebyshev_opts_parse
   public :: c_pb_ksp_chebyshev_set_opts, c_pb_solve_chebyshev
+  ! -pc_type mg: the level smoother (-mg_levels_ksp_type, -mg_levels_pc_type, ...)
+  public :: c_pb_pc_mg_opts_default, c_pb_pc_mg_opts_parse, c_pb_ksp_pc_mg_set_opts
+  public :: c_pb_ksp_pc_mg_get_opts, c_pb_solve_mg
 
   interface PoissboxAllreduceSum  ! ≙ MPI_Allreduce(..., MPI_SUM, MPI_COMM_WORLD)
      module procedure allreduce_sum_int, allreduce_sum_real
@@ -456,6 +469,36 @@ module poissbox_gpu
        type(pb_ksp_result) :: res
        integer(c_int64_t), value :: cap
      end function
+     integer(c_int) function c_pb_pc_mg_opts_default(o) bind(C, name="pb_pc_mg_opts_default")
+       import :: c_int, pb_pc_mg_opts
+       type(pb_pc_mg_opts) :: o
+     end function
+     integer(c_int) function c_pb_pc_mg_opts_parse(o, argc, argv) &
+          bind(C, name="pb_pc_mg_opts_parse")
+       import :: c_int, c_ptr, pb_pc_mg_opts
+       type(pb_pc_mg_opts) :: o
+       integer(c_int), value :: argc
+       type(c_ptr), dimension(*) :: argv
+     end function
+     integer(c_int) function c_pb_ksp_pc_mg_set_opts(ksp, o) bind(C, name="pb_ksp_pc_mg_set_opts")
+       import :: c_int, c_ptr, pb_pc_mg_opts
+       type(c_ptr), value :: ksp
+       type(pb_pc_mg_opts) :: o
+     end function
+     integer(c_int) function c_pb_ksp_pc_mg_get_opts(ksp, o) bind(C, name="pb_ksp_pc_mg_get_opts")
+       import :: c_int, c_ptr, pb_pc_mg_opts
+       type(c_ptr), value :: ksp
+       type(pb_pc_mg_opts) :: o
+     end function
+     integer(c_int) function c_pb_solve_mg(A, P, o, mo, b, x, res, hist, cap) &
+          bind(C, name="pb_solve_mg")
+       import :: c_int, c_ptr, c_int64_t, pb_ksp_opts, pb_pc_mg_opts, pb_ksp_result
+       type(c_ptr), value :: A, P, b, x, hist
+       type(pb_ksp_opts) :: o
+       type(pb_pc_mg_opts) :: mo
+       type(pb_ksp_result) :: res
+       integer(c_int64_t), value :: cap
+     end function
      integer(c_int) function c_pb_ksp_chebyshev_get_eigenvalues(ksp, emin, emax, estimated) &
           bind(C, name="pb_ksp_chebyshev_get_eigenvalues")
        import :: c_int, c_ptr, c_double
@@ -710,6 +753,7 @@ contains
     real(pb_dp), intent(out), optional :: rnorm
     type(pb_ksp_opts) :: o
     type(pb_ksp_chebyshev_opts) :: co
+    type(pb_pc_mg_opts) :: mo
     type(pb_ksp_result) :: res
     integer :: nargs, i, l, lmax
     character(len=:), allocatable, target :: args(:)
@@ -732,13 +776,20 @@ contains
     ierr = c_pb_ksp_opts_parse(o, int(nargs, c_int), argv)
     if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_default(co)
     if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_parse(co, int(nargs, c_int), argv)
+    if (ierr == 0) ierr = c_pb_pc_mg_opts_default(mo)
+    if (ierr == 0) ierr = c_pb_pc_mg_opts_parse(mo, int(nargs, c_int), argv)
     if (ierr /= 0) then
        call check(ierr, "KSPSetFromOptions")
        return
     end if
     if (c_associated(A%h, P%h) .eqv. .false.) print *, "Setting nullspace on A"
     ! (the Chebyshev settings are read by a KSP of that type only)
-    ierr = c_pb_solve_chebyshev(A%h, P%h, o, co, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
+    ! (-pc_type mg under another KSP type takes its level smoother, -mg_levels_*, instead)
+    if (o%pc_type == 3 .and. o%ksp_type /= 3) then
+       ierr = c_pb_solve_mg(A%h, P%h, o, mo, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
+    else
+       ierr = c_pb_solve_chebyshev(A%h, P%h, o, co, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
+    end if
     call check(ierr, "KSPSolve")
     if (present(its)) its = int(res%its)
     if (present(reason)) reason = int(res%reason)
