@@ -126,6 +126,56 @@ __device__ __forceinline__ void store_pts(__amdgpu_buffer_rsrc_t rs, unsigned of
 }
 
 // ---------------------------------------------------------------------------------------------
+// The update step of the stationary iterations, defined once: Richardson and Chebyshev as KSPs
+// (RichLoad / ChebLoad in pb_stencil.hip, rich_x_kernel / cheb_x_kernel in pb_ksp_stationary.hip)
+// and as the multigrid's Jacobi-type level smoothers (PolyLoad<N> in pb_stencil.hip, poly_value<N>
+// in pb_mg.hip). Every operation is rounded, in the order written here (no FMA contraction: the
+// build's -ffp-contract=off), so the fused engine passes and the vector kernels give the same
+// bits. SHIFT = false (the multigrid forms: no null-space shift): the add is absent, not + 0.0,
+// which would turn a -0.0 into +0.0.
+// (The compiler keeps or swaps a product's two operands by where each was defined, so the order
+// they are written in, and a step that calls another instead of spelling its sequence out,
+// change the engine kernels' code though not their results: cheb_step's z * scale and
+// poly_second_step's own sequence keep that code as it was tuned.)
+// ---------------------------------------------------------------------------------------------
+// x + scale (dinv q + shift)
+template <bool SHIFT>
+__device__ __forceinline__ double rich_step(double x, double q, double dinv, double shift,
+                                            double scale) {
+  double z = dinv * q;
+  if constexpr (SHIFT) z = z + shift;
+  const double u = scale * z;
+  return x + u;
+}
+// omega ((y - ym1) + scale (dinv q + shift)) + ym1
+template <bool SHIFT>
+__device__ __forceinline__ double cheb_step(double y, double ym1, double q, double dinv,
+                                            double shift, double scale, double omega) {
+  double z = dinv * q;
+  if constexpr (SHIFT) z = z + shift;
+  double t = y - ym1;
+  const double u = z * scale;
+  t = t + u;
+  t = omega * t;
+  return t + ym1;
+}
+// the level smoothers' zero-start cases: from y = ym1 = 0 with q = b, omega (scale (dinv b)),
+// and with ym1 = 0 (or Richardson: omega = 1), omega (y + scale (dinv q))
+__device__ __forceinline__ double poly_start_step(double b, double dinv, double scale,
+                                                  double omega) {
+  const double z = dinv * b;
+  const double u = scale * z;
+  return omega * u;
+}
+__device__ __forceinline__ double poly_second_step(double y, double q, double dinv, double scale,
+                                                   double omega) {
+  const double z = dinv * q;
+  const double u = scale * z;
+  const double t = y + u;
+  return omega * t;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Cross-lane helpers (DPP wave shifts: VALU only, no LDS traffic; bound_ctrl: the end lane
 // with no source reads 0, no old-value operand to initialise)
 // ---------------------------------------------------------------------------------------------

@@ -269,6 +269,14 @@ struct StencilPlanes {
   // instead of ghost planes (which then need not exist)
   bool wrap = false;
 };
+// one rank: no ghost planes, the periodic wrap read in place
+inline StencilPlanes wrap_planes() {
+  StencilPlanes gp;
+  gp.ghost_lo = gp.ghost_hi = nullptr;
+  gp.wrap = true;
+  return gp;
+}
+inline Star star_of(const pb_op* op) { return Star{op->cx, op->cy, op->cz, op->cc}; }
 enum { PLANES_ALL = 0, PLANES_INTERIOR = 1, PLANES_BOUNDARY = 2 };
 int launch_star7_apply(pb_grid* g, const Star& s, const double* x, double* y,
                        const StencilPlanes& gp, int mode);

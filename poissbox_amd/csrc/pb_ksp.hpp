@@ -1,0 +1,151 @@
+// pb_ksp.hpp -- struct pb_ksp and what the KSP's host files share: pb_solver.cpp (create / begin /
+// iterate / end, the CG enqueue paths), pb_ksp_stationary.cpp (richardson, chebyshev, preonly),
+// pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers) and
+// pb_op.cpp (the operator).
+#pragma once
+#include <vector>
+
+#include "pb_internal.hpp"
+
+struct pb_ksp {
+  pb_op* A = nullptr;
+  pb_op* P = nullptr;
+  pb_ksp_opts opts;
+  double* r = nullptr;
+  // Jacobi / none on the fused operator: pass B forms and stores p and writes the residual to
+  // the other buffer -- iteration i reads rbuf(i), writes rbuf(i + 1)
+  double* r2 = nullptr;
+  bool pst = false;
+  double* rbuf(int64_t i) const { return (pst && (i & 1)) ? r2 : r; }
+  // iteration i: p_old = pb[i % ns], p_new = pb[(i + 1) % ns]; ns = 2, or 4 with the depth-4
+  // deferred x update (pb[2], pb[3] allocated on first use)
+  double* pb[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* w = nullptr;   // generic (unfused) path only
+  double* z = nullptr;   // generic path only
+  // Richardson (-ksp_type richardson): update i reads xbuf(i) and writes xbuf(i + 1) -- the
+  // engine pass forms x_new at a point's neighbours from x_old there, so x is never updated in
+  // place; the caller's x is xbuf(even), and pb_ksp_end copies x2 back after an odd number of
+  // updates (the device's count: launches that exited at entry flipped nothing). Jacobi / none:
+  // r ping-pongs likewise (rich_rbuf), r_0 = b read in place from a zero guess.
+  // Chebyshev (-ksp_type chebyshev) runs as Richardson does (rich() covers both) with one more
+  // solution buffer: update i >= 1 reads y_i = xbuf(i) and y_(i-1) = xbuf(i - 1) and writes
+  // xbuf(i + 1), the three rotating; the caller's x is xbuf(0 mod 3)
+  struct Rich {
+    double* x2 = nullptr;
+    double* x3 = nullptr;
+    bool guess = false;  // this solve started from a nonzero guess (r_0 is in r, not b)
+  };
+  Rich ri;
+  bool cheb() const { return opts.ksp_type == PB_KSP_CHEBYSHEV; }
+  bool rich() const { return opts.ksp_type == PB_KSP_RICHARDSON || cheb(); }
+  double* xbuf(int64_t i) const {
+    if (cheb()) return i % 3 == 0 ? x->d : (i % 3 == 1 ? ri.x2 : ri.x3);
+    return (i & 1) ? ri.x2 : x->d;
+  }
+  const double* rich_rbuf(int64_t i) const {
+    return i == 0 && !ri.guess ? b->d : ((i & 1) ? r2 : r);
+  }
+  // Chebyshev's bounds in use and what follows from them (KSPSolve_Chebyshev's scale, mu,
+  // omegaprod); state: 0 = not set yet, 1 = the caller's, 2 = estimated for the deltas in `deltas`
+  // (A's, then P's: the estimate runs again when either changed)
+  struct Cheb {
+    pb_ksp_chebyshev_opts opts;  // pb_ksp_chebyshev_set_opts; the defaults from pb_ksp_create
+    int state = 0;
+    double emin = 0.0, emax = 0.0, scale = 0.0, mu = 0.0, omegaprod = 0.0;
+    double deltas[6] = {0, 0, 0, 0, 0, 0};
+  };
+  Cheb ch;
+  pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
+  pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
+  pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
+  int fold_nparts_b = 0;     // partial-sum blocks of the last folded pass B
+  bool stored_z() const { return mg || fft; }  // PCs whose z = M^-1 r is stored (not Jacobi)
+  bool lazy0 = false;  // r0 = b, x0 = 0, p0 = 0 left implicit by pb_ksp_begin
+  double* guess_bsums() const { return reinterpret_cast<double*>(d_st + 2); }
+  pb::CgState* d_st = nullptr;
+  double* d_hist = nullptr;
+  int64_t nhist = 0;
+  int* h_done = nullptr;      // host-mapped, one flag per host iteration (+1)
+  int* h_done_dev = nullptr;  // its device alias
+  int64_t done_cap = 0;
+  std::vector<hipEvent_t> ring;
+  // solve state
+  const pb_vec* b = nullptr;
+  pb_vec* x = nullptr;
+  int64_t host_iter = 0;
+  bool stopped = false;
+  bool begun = false;
+  int defer_x = 4;  // x updated every defer_x-th iteration (PB_CG_DEFER_X = 0, 2 or 4)
+  int pslots() const { return defer_x == 4 ? 4 : 2; }
+  // single-reduction iteration (-ksp_cg_single_reduction on the fused operator, Jacobi / none):
+  // the state alternates between the two slots d_st[0..1] within a pb_ksp_iterate batch (pass P
+  // of the batch's n-th iteration reads slot n & 1 and writes the other); nparts = pass S's
+  // partial-sum blocks of the last iteration (folded: reduced by the next pass P's prologue)
+  struct Sr {
+    bool on = false;
+    int nparts = 0;
+  };
+  Sr sr;
+  // projected initial guess (-ksp_guess_type fischer; PETSc KSPGuessFischer model 1): curl stored
+  // pairs (xt[i], bt[i] = A xt[i]) with the bt orthonormal in the 2-norm, and the last formed
+  // guess. d_coef: [0..15] the multi-dot's sums, [16] the new direction's norm^2
+  struct Fischer {
+    int maxl = 0, curl = 0;
+    std::vector<double*> xt, bt;
+    double* guess = nullptr;
+    double* d_coef = nullptr;
+  };
+  Fischer* fg = nullptr;
+};
+
+// (internal to the KSP's files: kept out of the library's dynamic symbols)
+#pragma GCC visibility push(hidden)
+namespace pb {
+
+// the fused CG passes evaluate A p inside the stencil engine (reference order); the assembled P
+// (AIJ order at the seams) runs the unfused iteration around its own MatMult
+inline bool fused_kind(int kind) { return kind == PB_OP_STAR7; }
+
+// ---- pb_op.cpp ----
+// y = A x without the entry point's argument checks
+int op_apply_raw(pb_op* op, const double* x, double* y);
+// KSP iterations enqueued ahead of the convergence poll: the operator kernels launched inside
+// the guard's scope exit at entry once the KSP's device flag is set (pb_ctx::op_skip)
+struct OpApplySkip {
+  pb_ctx* ctx;
+  OpApplySkip(pb_ctx* c, const int* flag) : ctx(c) { ctx->op_skip = flag; }
+  ~OpApplySkip() { ctx->op_skip = nullptr; }
+};
+
+// ---- pb_solver.cpp ----
+int ensure_done_cap(pb_ksp* k, int64_t need);
+// z = M^-1 r for the stored-z preconditioners; *np = residual-sum partial blocks written by the
+// PC itself (MG's last sweep), 0 if the caller must take the sums
+int pc_apply_dev(pb_ksp* k, const double* r, double* z, const int* skip, int* np);
+
+// ---- pb_options.cpp: every range and compatibility rule of the option structs ----
+// Chebyshev's interval: finite, non-zero, of one sign, emax > emin (`what` names it in the error)
+int check_cheb_pair(double emin, double emax, const char* what);
+int check_cheb_opts(const pb_ksp_chebyshev_opts* o);
+int check_mg_opts(const pb_pc_mg_opts* o);
+int check_guess_opts(int model, int maxl);
+int check_ref_norm_opts(const pb_ksp_opts* o);
+int check_richardson_scale(double scale);
+// the bounds the level smoother runs with: the caller's, or the esteig transform of D^-1 A's
+// exact extremes (0, 2) on every level
+void mg_levels_bounds(const pb_pc_mg_opts* o, double* emin, double* emax);
+
+// ---- pb_ksp_stationary.cpp: -ksp_type richardson | chebyshev (k->rich()) and preonly ----
+// pb_ksp_begin's setup (the state with the tolerances is on its way to k->d_st), one update of
+// pb_ksp_iterate, and pb_ksp_end's copy of the result into the caller's x after `its` updates
+int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x);
+int enqueue_rich_iteration(pb_ksp* k);
+int rich_copy_back(pb_ksp* k, int64_t its);
+int solve_preonly(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res);
+
+// ---- pb_ksp_guess.cpp: -ksp_guess_type fischer ----
+int solve_projected(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
+                    int64_t cap);
+
+}  // namespace pb
+#pragma GCC visibility pop

@@ -6,8 +6,8 @@
 // The hot step of Richardson on the 7-point operator is one stencil-engine pass (RichLoad /
 // RichEpi, pb_stencil.hip; Chebyshev: ChebLoad / RichEpi); the kernels here are its unfused form,
 // the steps around operators without an engine (compact, assembled, split grids) and the scalar
-// logic. The device-resident state, done flag, history and polling are CG's (CgState,
-// pb_solver.cpp).
+// logic; their host drivers are in pb_ksp_stationary.cpp. The device-resident state, done flag,
+// history and polling are CG's (CgState, pb_solver.cpp).
 #include "pb_cg_device.hpp"
 
 namespace pb {
@@ -139,14 +139,11 @@ __global__ __launch_bounds__(256) void rich_x_kernel(const double* __restrict__ 
   const double dinv = st->dinv, shift = -st->mu;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    double z = dinv * q[i];
-    z = z + shift;
-    const double u = scale * z;
-    x_out[i] = x[i] + u;
+    x_out[i] = rich_step<true>(x[i], q[i], dinv, shift, scale);
   }
 }
 
-// Chebyshev's update i >= 1, ChebLoad's expression (pb_stencil.hip) in its rounding order
+// Chebyshev's update i >= 1 (cheb_step, pb_device.hpp: ChebLoad in pb_stencil.hip calls the same)
 __global__ __launch_bounds__(256) void cheb_x_kernel(const double* __restrict__ y,
                                                      const double* __restrict__ ym1,
                                                      const double* __restrict__ q,
@@ -156,14 +153,8 @@ __global__ __launch_bounds__(256) void cheb_x_kernel(const double* __restrict__ 
   const double dinv = st->dinv, shift = -st->mu, omega = st->alpha;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    double z = dinv * q[i];
-    z = z + shift;
-    const double ykm1 = ym1[i];
-    double t = y[i] - ykm1;
-    const double u = scale * z;
-    t = t + u;
-    t = omega * t;
-    y_out[i] = t + ykm1;
+    const double qi = q[i], ykm1 = ym1[i];  // (read in the order the step uses them)
+    y_out[i] = cheb_step<true>(y[i], ykm1, qi, dinv, shift, scale, omega);
   }
 }
 

@@ -29,7 +29,7 @@
 #include <cmath>
 #include <vector>
 
-#include "pb_internal.hpp"
+#include "pb_device.hpp"
 
 namespace pb {
 
@@ -490,9 +490,10 @@ __global__ __launch_bounds__(256) void mg_prolong_z_kernel(MgGeo F, const double
 // ---------------------------------------------------------------------------------------------
 // Jacobi-type level smoothers (-mg_levels_pc_type jacobi under richardson or chebyshev). One step:
 //   y_new = omega ((y - yp) + scale (dinv r)) + yp,  dinv = 1 / cc,
-// every operation rounded, in PolyLoad's order (pb_stencil.hip), so the engine pass, the pair
-// kernel and the vector kernel give the same bits. N = 3: y, yp, r; N = 2: y, r (yp = 0 or
-// Richardson); N = 1: the zero start, from b alone.
+// every operation rounded in the order of its one definition (cheb_step, poly_second_step,
+// poly_start_step in pb_device.hpp, which PolyLoad in pb_stencil.hip calls too), so the engine
+// pass, the pair kernel and the vector kernel give the same bits. N = 3: y, yp, r; N = 2: y, r
+// (yp = 0 or Richardson); N = 1: the zero start, from b alone.
 // ---------------------------------------------------------------------------------------------
 struct PolyArgs {
   const double* a0;  // N = 1: b; else y
@@ -502,23 +503,9 @@ struct PolyArgs {
 };
 template <int N>
 __device__ __forceinline__ double poly_value(const PolyArgs& A, double v0, double v1, double v2) {
-  if constexpr (N == 1) {
-    const double z = A.dinv * v0;
-    const double u = A.scale * z;
-    return A.omega * u;
-  } else if constexpr (N == 2) {
-    const double z = A.dinv * v1;
-    const double u = A.scale * z;
-    const double t = v0 + u;
-    return A.omega * t;
-  } else {
-    const double z = A.dinv * v2;
-    double t = v0 - v1;
-    const double u = A.scale * z;
-    t = t + u;
-    t = A.omega * t;
-    return t + v1;
-  }
+  if constexpr (N == 1) return poly_start_step(v0, A.dinv, A.scale, A.omega);
+  else if constexpr (N == 2) return poly_second_step(v0, v1, A.dinv, A.scale, A.omega);
+  else return cheb_step<false>(v0, v1, v2, A.dinv, 0.0, A.scale, A.omega);
 }
 template <int N>
 __device__ __forceinline__ double poly_at(const PolyArgs& A, int64_t id) {

@@ -329,8 +329,8 @@ struct GuessInit {
 // and the residual in one pass. The field is x_new = x + scale (dinv q + shift), formed on load
 // from two raw arrays (q = r with Jacobi / no PC, the stored z = M^-1 r otherwise; shift = -mean,
 // the null-space removal), every product and sum rounded (no FMA contraction: the build's
-// -ffp-contract=off), so a vector kernel with the same expression gives the same bits
-// (rich_x_kernel, pb_ksp_stationary.hip). The epilogue stores the centre value x_new and
+// -ffp-contract=off; rich_step in pb_device.hpp is the one definition), so rich_x_kernel
+// (pb_ksp_stationary.hip) gives the same bits. The epilogue stores the centre value x_new and
 // r_new = b - A x_new (reference summation order) and, with SUMS (Jacobi / no PC), takes the sums
 // of t = dinv r_new - mean_old (t, t^2) behind the next iteration's norm and mean. x and (SUMS) r
 // go to other buffers than they are read from: neighbouring waves and blocks still read x_old and
@@ -352,18 +352,15 @@ struct RichLoad {
   }
   __device__ __forceinline__ const double* src(int a) const { return a == 0 ? x : q; }
   __device__ __forceinline__ double value(const double* raw) const {
-    double z = dinv * raw[1];
-    z = z + shift;
-    const double u = scale * z;
-    return raw[0] + u;
+    return rich_step<true>(raw[0], raw[1], dinv, shift, scale);
   }
 };
 // Chebyshev (-ksp_type chebyshev, PETSc KSPSolve_Chebyshev), update i >= 1: the field is
 // y_new = omega ((y - ym1) + scale (dinv q + shift)) + ym1, formed on load from three raw arrays
 // (omega = the state's alpha, advanced by the finalize before this pass), every operation rounded
-// in this order; cheb_x_kernel (pb_ksp_stationary.hip) is the same expression. RichEpi stores
-// y_new and r_new = b - A y_new: reads y, ym1, q, b and writes y, r, 48 B/DoF. y_new goes to a
-// third buffer: neighbouring waves and blocks still read y and ym1 around this point.
+// in cheb_step's order (pb_device.hpp), as in cheb_x_kernel (pb_ksp_stationary.hip). RichEpi
+// stores y_new and r_new = b - A y_new: reads y, ym1, q, b and writes y, r, 48 B/DoF. y_new goes
+// to a third buffer: neighbouring waves and blocks still read y and ym1 around this point.
 struct ChebLoad {
   static constexpr int NR = 3;
   static constexpr bool GHOST_RAW = false;
@@ -382,13 +379,7 @@ struct ChebLoad {
     return a == 0 ? y : (a == 1 ? ym1 : q);
   }
   __device__ __forceinline__ double value(const double* raw) const {
-    double z = dinv * raw[2];
-    z = z + shift;
-    double t = raw[0] - raw[1];
-    const double u = scale * z;
-    t = t + u;
-    t = omega * t;
-    return t + raw[1];
+    return cheb_step<true>(raw[0], raw[1], raw[2], dinv, shift, scale, omega);
   }
 };
 template <bool STOREX, bool SUMS>
@@ -433,9 +424,10 @@ struct RichEpi {
 // The Jacobi-type level smoothers of the multigrid (-mg_levels_pc_type jacobi under richardson or
 // chebyshev, pb_mg.hip): one smoothing step and its residual in one pass. The field is
 //   y_new = omega ((y - yp) + scale (dinv r)) + yp,
-// formed on load from up to three raw arrays, every operation rounded in this order
-// (mg_poly_kernel in pb_mg.hip is the same expression per pair). scale, omega and dinv = 1 / cc
-// are host-known constants passed by value: no state prologue, no mean shift, no sums.
+// formed on load from up to three raw arrays, every operation rounded in the order of cheb_step,
+// poly_second_step and poly_start_step (pb_device.hpp; poly_value in pb_mg.hip calls the same).
+// scale, omega and dinv = 1 / cc are host-known constants passed by value: no state prologue, no
+// mean shift, no sums.
 //   PolyLoad<3>: y, yp, r  (Chebyshev step i >= 2; 48 B/DoF with b and the two stores)
 //   PolyLoad<2>: y, r      (yp = 0 or Richardson: y - 0 and + 0 are exact, so the same bits)
 //   PolyLoad<1>: b         (the zero start, y = yp = 0 and r = b: neither is read; PolyEpi<true>
@@ -455,23 +447,9 @@ struct PolyLoad {
     return a == 0 ? a0 : (a == 1 ? a1 : a2);
   }
   __device__ __forceinline__ double value(const double* raw) const {
-    if constexpr (N == 1) {
-      const double z = dinv * raw[0];
-      const double u = scale * z;
-      return omega * u;
-    } else if constexpr (N == 2) {
-      const double z = dinv * raw[1];
-      const double u = scale * z;
-      const double t = raw[0] + u;
-      return omega * t;
-    } else {
-      const double z = dinv * raw[2];
-      double t = raw[0] - raw[1];
-      const double u = scale * z;
-      t = t + u;
-      t = omega * t;
-      return t + raw[1];
-    }
+    if constexpr (N == 1) return poly_start_step(raw[0], dinv, scale, omega);
+    else if constexpr (N == 2) return poly_second_step(raw[0], raw[1], dinv, scale, omega);
+    else return cheb_step<false>(raw[0], raw[1], raw[2], dinv, 0.0, scale, omega);
   }
 };
 template <bool QB>

@@ -1,5 +1,6 @@
 // host_check.cpp -- host sanitizer driver for the host logic of libpoissbox_gpu
-// (pb_runtime.cpp, pb_solver.cpp) built with -fsanitize=address,undefined on the host side only.
+// (pb_runtime.cpp, pb_options.cpp, pb_op.cpp, pb_solver.cpp and the KSP's other .cpp files) built
+// with -fsanitize=address,undefined on the host side only.
 // Runs without a GPU: option parsing, slab partition, argument validation and the error paths
 // of every entry point that must fail cleanly (no device, NULL handles) -- the code a caller
 // reaches before any kernel launches. Exit status 0 = clean.
@@ -69,6 +70,67 @@ int main() {
     pb_ksp_opts_default(&o);
     EXPECT(pb_ksp_opts_parse(&o, 6, v) == PB_OK && o.pc_type == PB_PC_MG && o.mg_levels == 4 &&
            o.max_it == 123);
+  }
+
+  // the chebyshev and mg parsers: lists and enum names are walked on the caller's strings
+  {
+    struct Line {
+      std::vector<const char*> argv;
+      int cheb, mg;
+    };
+    const int A = PB_ERR_ARG, U = PB_ERR_UNSUPPORTED;
+    const std::vector<Line> lines = {
+        {{"-ksp_chebyshev_eigenvalues", "0.1,1.1", "-ksp_chebyshev_esteig", "0,0.2,0,1.05"}, 0, 0},
+        {{"-ksp_chebyshev_eigenvalues", "-2,-0.5", "-ksp_chebyshev_esteig_steps", "64"}, 0, 0},
+        {{"-ksp_chebyshev_eigenvalues", "-1,2"}, A, 0},
+        {{"-ksp_chebyshev_eigenvalues", "1"}, A, 0},
+        {{"-ksp_chebyshev_eigenvalues", "1,2,"}, A, 0},
+        {{"-ksp_chebyshev_eigenvalues", ""}, A, 0},
+        {{"-ksp_chebyshev_esteig", "0,0.1,0,1.1,2"}, A, 0},
+        {{"-ksp_chebyshev_esteig", "0,nan,0,1"}, A, 0},
+        {{"-ksp_chebyshev_esteig", ",,,"}, A, 0},
+        {{"-ksp_chebyshev_esteig_steps", "65"}, A, 0},
+        {{"-ksp_chebyshev_esteig_noisy", "OFF"}, U, 0},
+        {{"-ksp_chebyshev_esteig_noisy"}, 0, 0},
+        {{"-ksp_chebyshev_esteig"}, 0, 0},
+        {{"-mg_levels_ksp_type", "chebyshev", "-mg_levels_pc_type", "jacobi",
+          "-mg_levels_ksp_max_it", "3", "-mg_levels_ksp_chebyshev_eigenvalues", "0.25,2.5",
+          "-mg_levels_ksp_chebyshev_esteig", "0,0.2,0,1.05", "-mg_levels_ksp_rtol", "1e-4"}, 0, 0},
+        {{"-mg_levels_ksp_type", "chebyshev", "-mg_levels_pc_type", "sor"}, 0, U},
+        {{"-mg_levels_ksp_type", ""}, 0, U},
+        {{"-mg_levels_pc_type", "ilu"}, 0, U},
+        {{"-mg_levels_ksp_richardson_scale", "0.5"}, 0, U},
+        {{"-mg_levels_ksp_max_it", "9"}, 0, A},
+        {{"-mg_levels_ksp_chebyshev_eigenvalues", "1,inf"}, 0, A},
+        {{"-mg_levels_ksp_chebyshev_eigenvalues", "1,x"}, 0, A},
+        {{"-mg_levels_ksp_chebyshev_esteig", "0,0.1,0"}, 0, A},
+        {{"-mg_levels_ksp_chebyshev_esteig", "0,0.1,0,1.1,"}, 0, A},
+        {{"-mg_", "-mg_levels_ksp_max_it"}, 0, 0}};
+    for (const Line& l : lines) {
+      pb_ksp_chebyshev_opts c, c0;
+      pb_pc_mg_opts m, m0;
+      EXPECT(pb_ksp_chebyshev_opts_default(&c) == PB_OK && pb_pc_mg_opts_default(&m) == PB_OK);
+      c0 = c;
+      m0 = m;
+      const int rc = pb_ksp_chebyshev_opts_parse(&c, (int)l.argv.size(), l.argv.data());
+      const int rm = pb_pc_mg_opts_parse(&m, (int)l.argv.size(), l.argv.data());
+      EXPECT(rc == l.cheb && rm == l.mg);
+      // an error leaves the struct as it was given
+      EXPECT(rc == PB_OK || (c.emin == c0.emin && c.emax == c0.emax &&
+                             c.esteig_steps == c0.esteig_steps &&
+                             !std::memcmp(c.esteig, c0.esteig, sizeof(c.esteig))));
+      EXPECT(rm == PB_OK || (m.levels_ksp_type == m0.levels_ksp_type &&
+                             m.levels_pc_type == m0.levels_pc_type &&
+                             m.levels_ksp_max_it == m0.levels_ksp_max_it &&
+                             m.levels_richardson_scale == m0.levels_richardson_scale &&
+                             !std::memcmp(m.levels_esteig, m0.levels_esteig,
+                                          sizeof(m.levels_esteig))));
+      pb_ksp_opts_default(&o);
+      EXPECT(pb_ksp_opts_parse(&o, (int)l.argv.size(), l.argv.data()) ==
+             (rc != PB_OK ? rc : rm));
+    }
+    EXPECT(pb_ksp_chebyshev_opts_parse(nullptr, 0, nullptr) == PB_ERR_ARG);
+    EXPECT(pb_pc_mg_opts_parse(nullptr, 0, nullptr) == PB_ERR_ARG);
   }
 
   // no GPU in the CPU tier: context creation must fail cleanly, never crash

@@ -1,6 +1,6 @@
 """CPU tier: host sanitizer builds (the reference's analogue is its Debug flags,
 CMakeLists.txt:17). The oracle (oracle/pb_oracle.c) and the host code of libpoissbox_gpu
-(pb_runtime.cpp, pb_solver.cpp, the host side of every .hip file; device code unchanged) are built
+(every .cpp file of poissbox_amd/csrc, the host side of every .hip file; device code unchanged) are built
 with -fsanitize=address,undefined and driven by tests/sanitize/*.c[pp] -- every restated routine on
 small odd shapes, and the library's option parsing, slab partition and argument/error paths without
 a GPU. Any out-of-bounds access, leak or undefined behaviour fails the run."""
