@@ -363,8 +363,9 @@ typedef struct {
 typedef struct {
   int reason;
   int64_t its;
-  double rnorm;      /* last ||z||_2 (KSP_NORM_PRECONDITIONED) */
-  double rnorm0;
+  double rnorm;      /* the last norm of the KSP's norm type (pb_ksp_set_norm_type): ||z||_2 by
+                        default (KSP_NORM_PRECONDITIONED), ||r||_2, sqrt(|r.z|), or 0 with none */
+  double rnorm0;     /* the stopping reference, in the same norm */
   int64_t nhist;     /* residual norms logged (≙ KSPGetResidualHistory's count): its + 1, or its
                         after a breakdown exit (beta = 0, indefinite PC / matrix) */
 } pb_ksp_result;
@@ -390,8 +391,9 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** ksp);
 /* KSPSolve(ksp, b, x): x0 = 0 (guess_zero; x is overwritten), or x0 = the x passed in with
  * initial_guess_nonzero (b and x must then be distinct vectors). A KSP may be reused: every
  * solve reads the flag and x afresh (a time loop warm-starts from the previous step's x).
- * history (optional, may be NULL): the res->nhist logged norms ||z_k|| (k = 0 .. nhist-1), at
- * most history_cap entries written. */
+ * history (optional, may be NULL): the res->nhist logged norms (k = 0 .. nhist-1) in the KSP's norm
+ * type -- ||z_k|| by default, ||r_k||, sqrt(|r_k.z_k|), or 0.0 with none (pb_ksp_set_norm_type) --
+ * at most history_cap entries written. */
 int pb_ksp_solve(pb_ksp* ksp, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
                  int64_t history_cap);
 /* Split form used by benchmarks: setup (r = b, or b - A x0 with a nonzero guess; z, ||z0||), then
@@ -401,6 +403,38 @@ int pb_ksp_begin(pb_ksp* ksp, const pb_vec* b, pb_vec* x);
 int pb_ksp_iterate(pb_ksp* ksp, int64_t iters);
 int pb_ksp_end(pb_ksp* ksp, pb_ksp_result* res, double* history, int64_t history_cap);
 int pb_ksp_destroy(pb_ksp* ksp);
+/* ≙ KSPSetNormType / -ksp_norm_type: the number the solve logs, tests and returns (history,
+ * pb_ksp_result.rnorm, rnorm0). z = N(M^-1 r) and the iteration (alpha, beta, p, x, r) are the same
+ * under every type; the values are PETSc's KSPNormType.
+ *   preconditioned (the default of cg / richardson / chebyshev): ||z_i||_2; from a nonzero guess the
+ *     reference is ||N(M^-1 b)||
+ *   unpreconditioned: ||r_i||_2 = ||b - A x_i||_2, the plain 2-norm (no mean shift); reference ||b||_2
+ *   natural (cg only): sqrt(|r_i . z_i|); reference sqrt(|b . N(M^-1 b)|)
+ *   none: no norm and no test (KSPConvergedSkip): the solve runs max_it iterations and ends with
+ *     PB_KSP_CONVERGED_ITS, its = max_it, rnorm = rnorm0 = 0 and its + 1 history entries of 0.0;
+ *     breakdown and NaN exits of the dots stay. pb_ksp_solve enqueues every iteration and waits once.
+ * ttol = max(rtol * rnorm0, atol), the rtol / atol / dtol / NaN tests and the reference-norm
+ * switches apply to the chosen number unchanged. No type adds a pass, a launch or a reduction to
+ * an iteration: ||r||^2 and r.z follow from the sums the passes already take (sor / mg / fft:
+ * sum r^2 is taken where the pass that forms r holds it in registers). One exception: the spectral
+ * PC's fused r update (compact A) gives way to the unfused pair under unpreconditioned. */
+enum pb_ksp_norm_type {
+  PB_KSP_NORM_DEFAULT = -1, PB_KSP_NORM_NONE = 0, PB_KSP_NORM_PRECONDITIONED = 1,
+  PB_KSP_NORM_UNPRECONDITIONED = 2, PB_KSP_NORM_NATURAL = 3
+};
+/* -ksp_norm_type none|preconditioned|unpreconditioned|natural|default from the same argument list
+ * as pb_ksp_opts_parse (which skips the option); the last occurrence wins, other options are
+ * ignored, the option as the last token without a value is skipped. An unknown word is
+ * PB_ERR_UNSUPPORTED and leaves *type as it was. */
+int pb_ksp_norm_type_parse(int* type, int argc, const char* const* argv);
+/* ≙ KSPSetNormType. PB_ERR_ARG for a value outside the enum; PB_ERR_UNSUPPORTED for natural on
+ * richardson / chebyshev (as PETSc refuses it) and for anything but default / none on preonly;
+ * PB_ERR_STATE between pb_ksp_begin and pb_ksp_end. An error leaves the KSP as it was. */
+int pb_ksp_set_norm_type(pb_ksp* ksp, int type);
+/* ≙ KSPGetNormType. *set: the value as set (PB_KSP_NORM_DEFAULT after create); *effective: the one
+ * in force (default: preconditioned for cg / richardson / chebyshev, none for preonly). Either
+ * may be NULL. */
+int pb_ksp_get_norm_type(const pb_ksp* ksp, int* set, int* effective);
 /* -ksp_chebyshev_eigenvalues emin,emax, -ksp_chebyshev_esteig a,b,c,d,
  * -ksp_chebyshev_esteig_steps n, -ksp_chebyshev_esteig_noisy [bool] from the same argument list
  * as pb_ksp_opts_parse; other options are ignored. */

@@ -120,6 +120,9 @@ _SIGS = {
     "pb_ksp_iterate": [c_p, c_i64],
     "pb_ksp_end": [c_p, C.POINTER(KspResult), P_d, c_i64],
     "pb_ksp_destroy": [c_p],
+    "pb_ksp_norm_type_parse": [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_char_p)],
+    "pb_ksp_set_norm_type": [c_p, C.c_int],
+    "pb_ksp_get_norm_type": [c_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pb_ksp_guess_form": [c_p, c_p, c_p],
     "pb_ksp_guess_update": [c_p, c_p, c_p],
     "pb_ksp_guess_reset": [c_p],

@@ -29,6 +29,9 @@ PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
 KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV = 0, 1, 2, 3
 # -mg_levels_ksp_type / -mg_levels_pc_type: the level smoother of -pc_type mg (pb_pc_mg_opts)
 MG_LEVELS_RICHARDSON, MG_LEVELS_CHEBYSHEV = 0, 1
+# pb_ksp_norm_type (PETSc's KSPNormType values)
+KSP_NORM_DEFAULT, KSP_NORM_NONE, KSP_NORM_PRECONDITIONED = -1, 0, 1
+KSP_NORM_UNPRECONDITIONED, KSP_NORM_NATURAL = 2, 3
 MG_LEVELS_SOR, MG_LEVELS_JACOBI = 0, 1
 
 REASONS = {0: "CONVERGED_ITERATING", 2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL",
@@ -384,7 +387,12 @@ class KspOptions(L.KspOpts):
     that struct. Likewise the multigrid's level smoother (pb_pc_mg_opts; `.mg`): mg_levels_ksp_type
     (MG_LEVELS_RICHARDSON | _CHEBYSHEV), mg_levels_pc_type (MG_LEVELS_SOR | _JACOBI),
     mg_levels_ksp_max_it, mg_levels_richardson_scale, mg_levels_eigenvalues, mg_levels_esteig;
-    KSP() sets them on a -pc_type mg KSP once one of them was touched or parsed."""
+    KSP() sets them on a -pc_type mg KSP once one of them was touched or parsed. Likewise
+    -ksp_norm_type (`.norm_type`, KSP_NORM_*; the C interface keeps it on the KSP object): KSP()
+    sets it unless it is KSP_NORM_DEFAULT."""
+
+    norm_type = property(lambda s: s.__dict__.get("norm_type", KSP_NORM_DEFAULT),
+                         lambda s, v: s.__dict__.__setitem__("norm_type", int(v)))
 
     def _mg(self):
         if "mg" not in self.__dict__:
@@ -451,6 +459,9 @@ def ksp_options(argv=(), **kw):
         L.call("pb_ksp_chebyshev_opts_parse", C.byref(o.chebyshev), len(argv), arr)
         if any(str(a).startswith("-mg_") for a in argv):
             L.call("pb_pc_mg_opts_parse", C.byref(o.mg), len(argv), arr)
+        nt = C.c_int(KSP_NORM_DEFAULT)
+        L.call("pb_ksp_norm_type_parse", C.byref(nt), len(argv), arr)
+        o.norm_type = nt.value
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -503,6 +514,25 @@ class KSP:
             except L.PbError:
                 self.destroy()
                 raise
+
+        if getattr(self.opts, "norm_type", KSP_NORM_DEFAULT) != KSP_NORM_DEFAULT:
+            try:
+                self.set_norm_type(self.opts.norm_type)
+            except L.PbError:
+                self.destroy()
+                raise
+
+    def set_norm_type(self, norm_type):
+        """KSPSetNormType: KSP_NORM_* (the number history, the tests and rnorm are taken in)."""
+        L.call("pb_ksp_set_norm_type", self.h, int(norm_type))
+
+    @property
+    def norm_type(self):
+        """(as set, in force): KSP_NORM_DEFAULT as set until set_norm_type; in force the default
+        is preconditioned (cg, richardson, chebyshev) or none (preonly)."""
+        s, e = C.c_int(), C.c_int()
+        L.call("pb_ksp_get_norm_type", self.h, C.byref(s), C.byref(e))
+        return s.value, e.value
 
     def pc_mg_set_opts(self, mg):
         """pb_ksp_pc_mg_set_opts: mg is a PcMgOpts (pc_mg_options())."""

@@ -49,6 +49,29 @@ __device__ __forceinline__ void wave_reduce_parts(const double* __restrict__ par
   }
 }
 
+// -ksp_norm_type: the logged / tested number dp of a residual-sum stage from the
+// sums S = (sum t, sum t^2, sum t.r, sum r) of t = dinv r - mu_old that every path takes already:
+//   preconditioned    ||z||     = sqrt(zz), zz the shifted sum of squares (the caller's, as before)
+//   natural           sqrt|r.z| = sqrt|zr|, zr the next beta (the caller's)
+//   unpreconditioned  ||r||, the plain 2-norm: sum t.r = dinv sum r^2 - mu_old sum r, so
+//                     sum r^2 = (S[2] + mu_old S[3]) / dinv -- Jacobi / no PC, where t is formed
+//                     from r by the pass itself (dinv = 1 / cc or 1, never 0); sor / mg / fft: S[4]
+//   none              0 (KSPConvergedSkip: no test either, see the stages)
+// The default comes first: the folded prologues of the hot passes run this on every wave.
+__device__ __forceinline__ double cg_dp(const CgState& st, const double* S, double zz, double zr,
+                                        double mu_old) {
+  if (st.norm == PB_KSP_NORM_PRECONDITIONED) return norm_from_sq(zz);
+  if (st.norm == PB_KSP_NORM_NATURAL) return sqrt(fabs(zr));
+  if (st.norm == PB_KSP_NORM_UNPRECONDITIONED) {
+    // a PC that stores z: t is z - mu_old, not a function of r -- sum r^2 comes as a fifth sum from
+    // the pass that formed r (RrParts, pb_internal.hpp; that iteration is never the single-reduction
+    // one, whose fifth sum is delta)
+    if (st.pc != PB_PC_NONE && st.pc != PB_PC_JACOBI) return norm_from_sq(S[4]);
+    return norm_from_sq((S[2] + mu_old * S[3]) / st.dinv);
+  }
+  return 0.0;
+}
+
 // how KSPConvergedDefault picks its reference norm when the solve starts from a nonzero guess
 enum { REF_RHS = 0, REF_INITIAL = 1, REF_MIN = 2, REF_ZERO_GUESS = 3 };
 
@@ -68,7 +91,8 @@ __device__ __forceinline__ void cg_stage0(CgState& st, const double* S, double* 
     zz = S[1] - N * delta * delta;
     zr = S[2] - delta * S[3];
   }
-  const double dp = norm_from_sq(zz);
+  const double dp = cg_dp(st, S, zz, zr, 0.0);
+  const bool skip = st.norm == PB_KSP_NORM_NONE;  // KSPConvergedSkip
   st.mu = mu;
   double rn0 = dp;
   if (ref == REF_RHS) rn0 = bnorm == 0.0 ? dp : bnorm;
@@ -91,10 +115,13 @@ __device__ __forceinline__ void cg_stage0(CgState& st, const double* S, double* 
     st.done = 1;
   } else {
     st.ttol = fmax(st.rtol * rn0, st.atol);
-    if (dp <= st.ttol) {
+    if (skip && st.max_it <= 0) {
+      st.reason = PB_KSP_CONVERGED_ITS;
+      st.done = 1;
+    } else if (!skip && dp <= st.ttol) {
       st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
       st.done = 1;
-    } else if (ref != REF_ZERO_GUESS && dp >= st.dtol * rn0) {
+    } else if (!skip && ref != REF_ZERO_GUESS && dp >= st.dtol * rn0) {
       st.reason = PB_KSP_DIVERGED_DTOL;
       st.done = 1;
     } else {
@@ -173,7 +200,8 @@ __device__ __forceinline__ void cg_stage2(CgState& st, const double* S, double* 
       zz = S[1] - N * delta * delta;
       zr = S[2] - delta * S[3];
     }
-    const double dp = norm_from_sq(zz);
+    const double dp = cg_dp(st, S, zz, zr, st.mu);
+    const bool skip = st.norm == PB_KSP_NORM_NONE;  // KSPConvergedSkip: its >= max_it alone
     // (single reduction: alpha_i was booked by cg_sr_top, before pass P applied it)
     if (!st.sr) cg_pend(st);
     st.dp = dp;
@@ -185,11 +213,20 @@ __device__ __forceinline__ void cg_stage2(CgState& st, const double* S, double* 
     if (!finite(dp)) {
       st.reason = PB_KSP_DIVERGED_NANORINF;
       st.done = 1;
-    } else if (dp <= st.ttol) {
+    } else if (!skip && dp <= st.ttol) {
       st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
       st.done = 1;
-    } else if (dp >= st.dtol * st.rnorm0) {
+    } else if (!skip && dp >= st.dtol * st.rnorm0) {
       st.reason = PB_KSP_DIVERGED_DTOL;
+      st.done = 1;
+    } else if (skip && i + 1 >= st.max_it) {
+      // (the test comes before beta's checks, as KSPSolve_CG calls it; the state still takes
+      // beta and the mean, so a split-form caller may raise nothing and read a complete state)
+      st.beta = zr;
+      st.mu = mu;
+      st.delta = S[4];
+      st.it = i + 1;
+      st.reason = PB_KSP_CONVERGED_ITS;
       st.done = 1;
     } else {
       st.beta = zr;
@@ -253,7 +290,7 @@ __device__ __forceinline__ void cg_copy(CgState& d, const CgState& s) {
   d.reason = s.reason, d.done = s.done, d.pc = s.pc, d.nullspace = s.nullspace;
   d.defer_x = s.defer_x;
   d.bbp = s.bbp;
-  d.delta = s.delta, d.sr = s.sr;
+  d.delta = s.delta, d.sr = s.sr, d.norm = s.norm;
 }
 static_assert(sizeof(CgState) == 248, "cg_copy lists every CgState field");
 

@@ -336,7 +336,22 @@ struct CgState {
   // z'z, z'r in the one reduction per iteration); sr = 1 selects that iteration's scalar logic
   double delta;
   int sr;
+  // -ksp_norm_type (pb_ksp_norm_type, never DEFAULT here): the number the stages log and test
+  int norm;
 };
+// -ksp_norm_type unpreconditioned with a PC that stores z (sor, mg, fft): the
+// pass that forms r leaves partial sums behind sum r^2 in a second region, the upper half of
+// ctx->d_partials (the PC's own four sums fill the lower half after it), and the finalize that
+// runs anyway reduces both. width says what a block wrote:
+//   1: sum r^2 (cg_pc_xr, cg_rr)         2: sum r^2, sum b^2 (cg_guess_resid; Richardson: t, t^2)
+//   4: pass B's t, t^2, t.r, r with t = r - mu: sum r^2 = sum t.r + mu sum r
+struct RrParts {
+  const double* parts = nullptr;
+  int nparts = 0, width = 0;
+};
+inline double* rr_region(const pb_ctx* ctx) { return ctx->d_partials + ctx->partials_cap / 2; }
+// (in blocks of ns sums, as launch_any's part_off)
+inline int rr_part_off(const pb_ctx* ctx, int ns) { return (int)(ctx->partials_cap / 2 / ns); }
 int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, CgState* st,
                    double dinv, double* hist, int* h_done);
 // Setup from a nonzero initial guess (-ksp_initial_guess_nonzero; x0 is never written):
@@ -352,10 +367,11 @@ int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p,
 int launch_cg_guess_init(pb_grid* g, const Star& s, const double* x0, const double* b, double* r,
                          double* p, const StencilPlanes& gp, double dinv, int mode, int part_off,
                          int* nblocks);
+// rr != nullptr (nparts == nullptr): sum r^2, sum b^2 per block into rr_region (RrParts width 2)
 int launch_cg_guess_resid(pb_grid* g, const double* b, const double* w, double* r, double* p,
-                          double dinv, int* nparts);
+                          double dinv, int* nparts, RrParts* rr = nullptr);
 int cg_finalize_guess(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
-                      CgState* st, double* hist, int* h_done);
+                      CgState* st, double* hist, int* h_done, const RrParts& rr = RrParts{});
 struct Fold {
   // 0: no fold; 1: stage 1 (pass B); 2: stage 2 (pass A); single-reduction pass P: 3: the
   // residual-sum stage of the previous iteration, then the top of this one; 4: the top only
@@ -398,7 +414,7 @@ int cg_finalize_pass_a(pb_ctx* ctx, int nparts, CgState* st);
 int launch_cg_pass_b(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
                      double* x, double* r, const StencilPlanes& gp, CgState* st, double* hist,
                      int* h_done, int64_t host_iter, int defer, bool finalize = true,
-                     const PStore& ps = PStore{});
+                     const PStore& ps = PStore{}, RrParts* rr = nullptr);
 int launch_cg_flush(pb_grid* g, double* x, const double* p, double alpha);
 // Folded single-rank Jacobi iteration (finalize in the passes' prologues, pb_stencil.hip): state
 // in two slots st2[0..1]; pass A of iteration host_iter >= 1 runs stage 2 of host_iter - 1
@@ -564,7 +580,7 @@ int launch_cg_generic_dot(pb_grid* g, const double* p, const double* w, CgState*
 int launch_cg_generic_xr(pb_grid* g, const double* p, const double* w, double* x, double* r,
                          CgState* st, int* nparts);
 int cg_finalize_stage2(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
-                       int64_t host_iter);
+                       int64_t host_iter, const RrParts& rr = RrParts{});
 
 // ---- vector ops (pb_vecops.hip) ----
 int vec_fill(pb_ctx* ctx, double* d, int64_t n, double a);
@@ -608,10 +624,14 @@ int grid_create_part(pb_ctx* ctx, const int64_t n[3], const double L[3], int64_t
                      pb_grid** out);
 
 // ---- preconditioned CG pieces (pb_cg_generic.hip) ----
+// rr != nullptr: sum r^2 of the new residual per block into rr_region (RrParts width 1)
 int launch_cg_pc_xr(pb_grid* g, const double* p, const double* w, double* x, const double* r_in,
-                    double* r, CgState* st, int first);
+                    double* r, CgState* st, int first, RrParts* rr = nullptr);
 int launch_cg_pc_sums(pb_grid* g, const double* z, const double* r, CgState* st, int* nparts);
-int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done);
+// sum r^2 per block into rr_region (the setup from a zero guess: r_0 = b)
+int launch_cg_rr(pb_grid* g, const double* r, RrParts* rr);
+int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
+                     const RrParts& rr = RrParts{});
 
 // ---- stationary solves: -ksp_type richardson / preonly (pb_ksp_stationary.hip, and the engine
 // pass launch_rich_update in pb_stencil.hip) ----
@@ -619,33 +639,39 @@ int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_
 // it = its = updates done, dp, rnorm0, ttol, reason, done, nlog), history buffer and done flags.
 int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double* q,
                        const double* b, double* x_out, double* r_out, const StencilPlanes& gp,
-                       const CgState* st, double scale, bool sums, bool skip, int* nparts);
+                       const CgState* st, double scale, bool sums, bool skip, int* nparts,
+                       int part_off = 0);
 // x_out = x + scale (dinv q - mean): RichLoad's expression, every product and sum rounded
 int launch_rich_x(pb_grid* g, const double* x, const double* q, double* x_out, const CgState* st,
                   double scale);
 // r = b - w (w = A x from the operator); nparts != nullptr: the two sums of dinv r - mean
+// (parts: where the sums go; nullptr: ctx->d_partials)
 int launch_rich_resid(pb_grid* g, const double* b, const double* w, double* r, const CgState* st,
-                      bool skip, int* nparts);
+                      bool skip, int* nparts, double* parts = nullptr);
 // the two sums of dinv q - mean (setup: q = b or the stored z)
-int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts);
+int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts,
+                     double* parts = nullptr);
 // `width` sums per block (only t, t^2 are read) of ctx->d_partials reduced and allreduced into
 // ctx->d_scalars; dst != nullptr: the first two copied there (the reference norm's sums of M^-1 b)
-int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst);
+int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst,
+                const RrParts& rr = RrParts{});
 // the norm, history entry, KSPConvergedDefault test and iteration limit after the setup
 // (host_iter = -1; ref = REF_*, bsums as cg_finalize_guess) or after update host_iter
 // cheb_mu != 0 (-ksp_type chebyshev): a test that gives nothing also advances the ratio
 // recurrence for the update that follows: st->beta = rho_i = 1 / (2 mu - rho_(i-1)) (rho_0 =
 // 1 / mu), st->alpha = omega_i = omegaprod rho_i -- CG's two fields, unused by these solves
+// rr (unpreconditioned norm with a stored-z PC): the two sums of t = r - mean the residual pass
+// left in the second partial region (RrParts width 2), behind ||r||
 int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
                   double* hist, int* h_done, int64_t host_iter, double cheb_mu = 0.0,
-                  double cheb_omegaprod = 0.0);
+                  double cheb_omegaprod = 0.0, const RrParts& rr = RrParts{});
 // Chebyshev's update i >= 1 (pb_stencil.hip ChebLoad): y_out = omega ((y - ym1) + scale (dinv q -
 // mean)) + ym1 with omega = st->alpha, r_out = b - A y_out, one rank, wrap planes; sums as
 // launch_rich_update's. Update 0 is launch_rich_update with Chebyshev's scale
 int launch_cheb_update(pb_grid* g, const Star& s, const double* y, const double* ym1,
                        const double* q, const double* b, double* y_out, double* r_out,
                        const StencilPlanes& gp, const CgState* st, double scale, bool sums,
-                       int* nparts);
+                       int* nparts, int part_off = 0);
 // the same expression as a vector kernel (the unfused form: split grids, compact / assembled
 // operators, tuning cheb_fused = 0)
 int launch_cheb_x(pb_grid* g, const double* y, const double* ym1, const double* q, double* y_out,

@@ -1,7 +1,7 @@
 // pb_ksp.hpp -- struct pb_ksp and what the KSP's host files share: pb_solver.cpp (create / begin /
 // iterate / end, the CG enqueue paths), pb_ksp_stationary.cpp (richardson, chebyshev, preonly),
-// pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers) and
-// pb_op.cpp (the operator).
+// pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers),
+// pb_norm_type.cpp (-ksp_norm_type) and pb_op.cpp (the operator).
 #pragma once
 #include <vector>
 
@@ -11,6 +11,19 @@ struct pb_ksp {
   pb_op* A = nullptr;
   pb_op* P = nullptr;
   pb_ksp_opts opts;
+  // -ksp_norm_type as set (pb_ksp_set_norm_type; pb_norm_type.cpp) and the one in force
+  int norm_type = PB_KSP_NORM_DEFAULT;
+  int norm() const {
+    if (norm_type != PB_KSP_NORM_DEFAULT) return norm_type;
+    return opts.ksp_type == PB_KSP_PREONLY ? PB_KSP_NORM_NONE : PB_KSP_NORM_PRECONDITIONED;
+  }
+  // none (KSPConvergedSkip): nothing but a breakdown ends the solve before max_it, so the host
+  // neither polls nor enqueues past it
+  bool norm_none() const { return norm() == PB_KSP_NORM_NONE; }
+  bool norm_unp() const { return norm() == PB_KSP_NORM_UNPRECONDITIONED; }
+  int64_t solve_iters() const {
+    return norm_none() ? opts.max_it : opts.max_it + 2 * (int64_t)opts.check_every;
+  }
   double* r = nullptr;
   // Jacobi / none on the fused operator: pass B forms and stores p and writes the residual to
   // the other buffer -- iteration i reads rbuf(i), writes rbuf(i + 1)

@@ -142,7 +142,7 @@ int pb::solve_projected(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* re
   const int rc = pb_ksp_begin(k, b, x);
   k->opts.initial_guess_nonzero = user_flag;
   PB_TRY(rc);
-  PB_TRY(pb_ksp_iterate(k, k->opts.max_it + 2 * (int64_t)k->opts.check_every));
+  PB_TRY(pb_ksp_iterate(k, k->solve_iters()));
   pb_ksp_result r;
   PB_TRY(pb_ksp_end(k, &r, history, cap));
   if (res) *res = r;

@@ -15,23 +15,37 @@ static bool rich_engine(const pb_ksp* k) {
   return fused_kind(k->A->kind) && !k->A->grid->ctx->split;
 }
 
-// r_out = b - A x (+ the sums of dinv r_out - mean with Jacobi / no PC: *np blocks, else 0)
-static int rich_residual(pb_ksp* k, const double* x, double* r_out, bool skip, int* np) {
+// the unpreconditioned norm with a stored-z PC: the residual pass takes its two sums of
+// t = r - mean (dinv = 1) after all, into the second partial region (the PC's own follow below it)
+static bool rich_rr(const pb_ksp* k) { return k->stored_z() && k->norm_unp(); }
+
+// r_out = b - A x (+ the sums of dinv r_out - mean with Jacobi / no PC: *np blocks, else 0; rr:
+// the same sums into the second region instead, rich_rr)
+static int rich_residual(pb_ksp* k, const double* x, double* r_out, bool skip, int* np,
+                         RrParts* rr) {
   pb_grid* g = k->A->grid;
   pb_ctx* ctx = g->ctx;
   const bool sums = !k->stored_z();
+  const bool aside = rich_rr(k);
+  int n2 = 0;
   *np = 0;
   if (rich_engine(k)) {
     const Star s = star_of(k->A);
     const StencilPlanes gp = wrap_planes();
-    return launch_rich_update(g, s, x, nullptr, k->b->d, nullptr, r_out, gp, k->d_st, 0.0, sums,
-                              skip, np);
+    PB_TRY(launch_rich_update(g, s, x, nullptr, k->b->d, nullptr, r_out, gp, k->d_st, 0.0,
+                              sums || aside, skip, aside ? &n2 : np,
+                              aside ? rr_part_off(ctx, 2) : 0));
+  } else {
+    {
+      OpApplySkip guard(ctx, skip ? &k->d_st->done : nullptr);
+      PB_TRY(op_apply_raw(k->A, x, k->w));
+    }
+    PB_TRY(launch_rich_resid(g, k->b->d, k->w, r_out, k->d_st, skip,
+                             aside ? &n2 : (sums ? np : nullptr),
+                             aside ? rr_region(ctx) : nullptr));
   }
-  {
-    OpApplySkip guard(ctx, skip ? &k->d_st->done : nullptr);
-    PB_TRY(op_apply_raw(k->A, x, k->w));
-  }
-  return launch_rich_resid(g, k->b->d, k->w, r_out, k->d_st, skip, sums ? np : nullptr);
+  if (aside) *rr = RrParts{rr_region(ctx), n2, 2};
+  return PB_OK;
 }
 
 // z = M^-1 r of a stored-z PC with the sums of z - mean (4 wide: the PC's own, or CG's sum kernel)
@@ -196,28 +210,38 @@ int pb::rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   k->ri.guess = k->opts.initial_guess_nonzero != 0;
   const int width = k->stored_z() ? 4 : 2;
   int np = 0;
+  RrParts rr;
   if (!k->ri.guess) {
     PB_HIP(hipMemsetAsync(x->d, 0, vb, ctx->stream));
+    if (rich_rr(k)) {  // ||r_0|| = ||b||: a reduction pass of its own (setup only)
+      int n2 = 0;
+      PB_TRY(launch_rich_sums(g, b->d, k->d_st, &n2, rr_region(ctx)));
+      rr = RrParts{rr_region(ctx), n2, 2};
+    }
     if (k->stored_z()) PB_TRY(rich_pc(k, b->d, nullptr, &np));
     else PB_TRY(launch_rich_sums(g, b->d, k->d_st, &np));
     return rich_finalize(ctx, np, width, nullptr, 3, k->d_st, k->d_hist, k->h_done_dev, -1, cmu,
-                         cop);
+                         cop, rr);
   }
   PB_TRY(check_ref_norm_opts(&k->opts));
   const int ref = k->opts.converged_use_initial_residual_norm
                       ? 1
                       : (k->opts.converged_use_min_initial_residual_norm ? 2 : 0);
   const double* bsums = nullptr;
-  if (ref != 1) {  // the reference norm ||N(M^-1 b)||: the sums of M^-1 b kept aside
-    if (k->stored_z()) PB_TRY(rich_pc(k, b->d, nullptr, &np));
+  // the reference norm ||N(M^-1 b)||: the sums of M^-1 b kept aside (unpreconditioned, Jacobi / no
+  // PC: ||b|| from the same sums of dinv b; none: no reference)
+  if (ref != 1 && !k->norm_none()) {
+    // (unpreconditioned with a stored-z PC: ||b|| from the plain sums of b, no PC application)
+    const bool pc = k->stored_z() && !k->norm_unp();
+    if (pc) PB_TRY(rich_pc(k, b->d, nullptr, &np));
     else PB_TRY(launch_rich_sums(g, b->d, k->d_st, &np));
-    PB_TRY(rich_reduce(ctx, np, width, k->guess_bsums()));
+    PB_TRY(rich_reduce(ctx, np, pc ? 4 : 2, k->guess_bsums()));
     bsums = k->guess_bsums();
   }
-  PB_TRY(rich_residual(k, x->d, k->r, false, &np));
+  PB_TRY(rich_residual(k, x->d, k->r, false, &np, &rr));
   if (k->stored_z()) PB_TRY(rich_pc(k, k->r, nullptr, &np));
   return rich_finalize(ctx, np, width, bsums, ref, k->d_st, k->d_hist, k->h_done_dev, -1, cmu,
-                       cop);
+                       cop, rr);
 }
 
 // one update: x_new = x + scale (M^-1 r - mean), r_new = b - A x_new, z_new and its sums, the
@@ -239,23 +263,29 @@ int pb::enqueue_rich_iteration(pb_ksp* k) {
   const double* xm1 = cheb && i >= 1 ? k->xbuf(i - 1) : nullptr;
   const bool fused = rich_engine(k) && (cheb ? tune("cheb_fused", 1) : tune("rich_fused", 1)) != 0;
   int np = 0;
+  RrParts rr;
   if (fused) {
     const Star s = star_of(k->A);
     const StencilPlanes gp = wrap_planes();
+    // (rich_rr: the sums variant of the same pass, its partials in the second region)
+    const bool aside = rich_rr(k);
+    const int off = aside ? rr_part_off(ctx, 2) : 0;
+    int n2 = 0;
     if (xm1)
       PB_TRY(launch_cheb_update(g, s, xin, xm1, q, k->b->d, xout, r_out, gp, k->d_st, scale,
-                                !k->stored_z(), &np));
+                                !k->stored_z() || aside, aside ? &n2 : &np, off));
     else
       PB_TRY(launch_rich_update(g, s, xin, q, k->b->d, xout, r_out, gp, k->d_st, scale,
-                                !k->stored_z(), true, &np));
+                                !k->stored_z() || aside, true, aside ? &n2 : &np, off));
+    if (aside) rr = RrParts{rr_region(ctx), n2, 2};
   } else {
     if (xm1) PB_TRY(launch_cheb_x(g, xin, xm1, q, xout, k->d_st, scale));
     else PB_TRY(launch_rich_x(g, xin, q, xout, k->d_st, scale));
-    PB_TRY(rich_residual(k, xout, r_out, true, &np));
+    PB_TRY(rich_residual(k, xout, r_out, true, &np, &rr));
   }
   if (k->stored_z()) PB_TRY(rich_pc(k, r_out, &k->d_st->done, &np));
   return rich_finalize(ctx, np, k->stored_z() ? 4 : 2, nullptr, 0, k->d_st, k->d_hist,
-                       k->h_done_dev, i, cheb ? k->ch.mu : 0.0, cheb ? k->ch.omegaprod : 0.0);
+                       k->h_done_dev, i, cheb ? k->ch.mu : 0.0, cheb ? k->ch.omegaprod : 0.0, rr);
 }
 
 // KSPSolve_PREONLY: x = N(M^-1 b). No norm, no reduction but the mean's, no NaN check. The

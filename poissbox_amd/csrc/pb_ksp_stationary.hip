@@ -23,7 +23,7 @@ namespace pb {
 __device__ __forceinline__ void rich_stage(CgState& st, const double* S, bool setup, int ref,
                                            double bnorm, double* hist, int* h_done,
                                            int64_t host_iter, double cheb_mu,
-                                           double cheb_omegaprod) {
+                                           double cheb_omegaprod, const double* Q = nullptr) {
   if (setup) {
     st.it = 0;
     st.its = 0;
@@ -42,7 +42,18 @@ __device__ __forceinline__ void rich_stage(CgState& st, const double* S, bool se
       delta = S[0] / N;
       zz = S[1] - N * delta * delta;
     }
-    const double dp = norm_from_sq(zz);
+    // -ksp_norm_type: unpreconditioned is ||r_i|| = ||b - A x_i||, the plain
+    // 2-norm, from the same two sums (Jacobi / no PC: t = dinv r - mean_old, so
+    // sum r^2 = (sum t^2 + 2 mean_old sum t + N mean_old^2) / dinv^2; a stored-z PC: the residual
+    // pass took the same two sums of t = r - mean_old aside, Q, dinv = 1); none: no norm, no test
+    const bool skip = st.norm == PB_KSP_NORM_NONE;
+    double dp = 0.0;
+    if (st.norm == PB_KSP_NORM_PRECONDITIONED) {
+      dp = norm_from_sq(zz);
+    } else if (st.norm == PB_KSP_NORM_UNPRECONDITIONED) {
+      const double* T = Q ? Q : S;
+      dp = norm_from_sq((T[1] + st.mu * (2.0 * T[0] + N * st.mu)) / (st.dinv * st.dinv));
+    }
     st.it = i;
     st.its = i;
     st.dp = dp;
@@ -60,15 +71,15 @@ __device__ __forceinline__ void rich_stage(CgState& st, const double* S, bool se
     if (!finite(dp)) {
       st.reason = PB_KSP_DIVERGED_NANORINF;
       st.done = 1;
-    } else if (dp <= st.ttol) {
+    } else if (!skip && dp <= st.ttol) {
       st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
       st.done = 1;
-    } else if (!(setup && ref == REF_ZERO_GUESS) && dp >= st.dtol * st.rnorm0) {
+    } else if (!skip && !(setup && ref == REF_ZERO_GUESS) && dp >= st.dtol * st.rnorm0) {
       // (from a zero guess ||z_0|| is the reference itself: no test at i = 0, as CG's stage 0)
       st.reason = PB_KSP_DIVERGED_DTOL;
       st.done = 1;
     } else if (i >= st.max_it) {
-      st.reason = PB_KSP_DIVERGED_ITS;
+      st.reason = skip ? PB_KSP_CONVERGED_ITS : PB_KSP_DIVERGED_ITS;  // (KSPConvergedSkip)
       st.done = 1;
     } else {
       st.mu = st.mu + delta;
@@ -93,7 +104,25 @@ __global__ __launch_bounds__(256) void rich_finalize_kernel(const double* __rest
                                                             int mode, const double* bsums, int ref,
                                                             CgState* st, double* hist, int* h_done,
                                                             int64_t host_iter, double cheb_mu,
-                                                            double cheb_omegaprod) {
+                                                            double cheb_omegaprod, RrParts rr) {
+  if ((mode & 1) && rr.parts) {  // the second region's two sums -> sums[2..3], same fixed order
+    __shared__ double red2[256][2];
+    for (int s = 0; s < 2; ++s) {
+      double v = 0.0;
+      for (int b = threadIdx.x; b < rr.nparts; b += 256) v += rr.parts[(int64_t)b * 2 + s];
+      red2[threadIdx.x][s] = v;
+    }
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+      if ((int)threadIdx.x < off)
+        for (int s = 0; s < 2; ++s) red2[threadIdx.x][s] += red2[threadIdx.x + off][s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      sums[2] = red2[0][0];
+      sums[3] = red2[0][1];
+    }
+  }
   if (mode & 1) {
     __shared__ double red[256][2];
     for (int s = 0; s < 2; ++s) {
@@ -116,15 +145,19 @@ __global__ __launch_bounds__(256) void rich_finalize_kernel(const double* __rest
   const double S[2] = {sums[0], sums[1]};
   const bool setup = host_iter < 0;
   double bnorm = 0.0;
-  if (setup && (ref == REF_RHS || ref == REF_MIN)) {
+  if (setup && (ref == REF_RHS || ref == REF_MIN) && st->norm != PB_KSP_NORM_NONE) {
     double zz = bsums[1];
-    if (st->nullspace) {
+    if (st->norm == PB_KSP_NORM_UNPRECONDITIONED) {
+      zz = bsums[1] / (st->dinv * st->dinv);  // ||b||^2 from the sums of dinv b: no PC application
+    } else if (st->nullspace) {
       const double delta = bsums[0] / st->ntot;
       zz = bsums[1] - st->ntot * delta * delta;
     }
     bnorm = norm_from_sq(zz);
   }
-  rich_stage(*st, S, setup, ref, bnorm, hist, h_done, host_iter, cheb_mu, cheb_omegaprod);
+  const double Q[2] = {sums[2], sums[3]};
+  rich_stage(*st, S, setup, ref, bnorm, hist, h_done, host_iter, cheb_mu, cheb_omegaprod,
+             rr.parts ? Q : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -243,12 +276,12 @@ int launch_cheb_x(pb_grid* g, const double* y, const double* ym1, const double* 
 }
 
 int launch_rich_resid(pb_grid* g, const double* b, const double* w, double* r, const CgState* st,
-                      bool skip, int* nparts) {
+                      bool skip, int* nparts, double* parts) {
   ScopedTimer tm(g->ctx, "rich_resid_vec");
-  const int nb = vec_blocks(g->ctx, g->nlocal);
+  const int nb = vec_blocks(g->ctx, g->nlocal);  // (<= 8 blocks per CU x 2 sums: fits either region)
   if (nparts) {
     hipLaunchKernelGGL(rich_resid_kernel<true>, dim3(nb), dim3(256), 0, g->ctx->stream, b, w, r,
-                       g->nlocal, g->ctx->d_partials, st, skip ? 1 : 0);
+                       g->nlocal, parts ? parts : g->ctx->d_partials, st, skip ? 1 : 0);
     *nparts = nb;
   } else {
     hipLaunchKernelGGL(rich_resid_kernel<false>, dim3(nb), dim3(256), 0, g->ctx->stream, b, w, r,
@@ -258,22 +291,23 @@ int launch_rich_resid(pb_grid* g, const double* b, const double* w, double* r, c
   return PB_OK;
 }
 
-int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts) {
+int launch_rich_sums(pb_grid* g, const double* q, const CgState* st, int* nparts, double* parts) {
+  ScopedTimer tm(g->ctx, "rich_sums");
   const int nb = vec_blocks(g->ctx, g->nlocal);
   hipLaunchKernelGGL(rich_sums_kernel, dim3(nb), dim3(256), 0, g->ctx->stream, q, g->nlocal,
-                     g->ctx->d_partials, st);
+                     parts ? parts : g->ctx->d_partials, st);
   PB_HIP(hipGetLastError());
   *nparts = nb;
   return PB_OK;
 }
 
-int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst) {
+int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst, const RrParts& rr) {
   hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      (const double*)ctx->d_partials, nparts, width, ctx->d_scalars, 1,
                      (const double*)nullptr, 0, (CgState*)nullptr, (double*)nullptr,
-                     (int*)nullptr, (int64_t)0, 0.0, 0.0);
+                     (int*)nullptr, (int64_t)0, 0.0, 0.0, rr);
   PB_HIP(hipGetLastError());
-  if (ctx->split) PB_TRY(allreduce_device(ctx, ctx->d_scalars, 2));
+  if (ctx->split) PB_TRY(allreduce_device(ctx, ctx->d_scalars, rr.parts ? 4 : 2));
   if (dst)
     PB_HIP(hipMemcpyAsync(dst, ctx->d_scalars, 2 * sizeof(double), hipMemcpyDeviceToDevice,
                           ctx->stream));
@@ -282,19 +316,23 @@ int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst) {
 
 int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
                   double* hist, int* h_done, int64_t host_iter, double cheb_mu,
-                  double cheb_omegaprod) {
+                  double cheb_omegaprod, const RrParts& rr) {
+  ScopedTimer tm(ctx, "rich_finalize");  // (with its allreduce on several ranks)
   const double* parts = ctx->d_partials;
+  // (the PC's own partials must have stayed below the second region)
+  if (rr.parts && ((int64_t)nparts * width > ctx->partials_cap / 2 || rr.width != 2))
+    return set_error(PB_ERR_UNSUPPORTED, "unpreconditioned norm: partial sums do not fit");
   if (!ctx->split) {
     hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
                        width, ctx->d_scalars, 3, bsums, ref, st, hist, h_done, host_iter, cheb_mu,
-                       cheb_omegaprod);
+                       cheb_omegaprod, rr);
     PB_HIP(hipGetLastError());
     return PB_OK;
   }
-  PB_TRY(rich_reduce(ctx, nparts, width, nullptr));
+  PB_TRY(rich_reduce(ctx, nparts, width, nullptr, rr));
   hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
                      width, ctx->d_scalars, 2, bsums, ref, st, hist, h_done, host_iter, cheb_mu,
-                     cheb_omegaprod);
+                     cheb_omegaprod, rr);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }

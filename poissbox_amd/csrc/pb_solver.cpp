@@ -1,7 +1,8 @@
 // pb_solver.cpp -- KSP (KSPSolve_CG analogue) host logic: pb_ksp_create / begin / iterate / end /
 // solve / destroy, the CG enqueue paths and pb_solve*. The operator is in pb_op.cpp, the options in
 // pb_options.cpp, -ksp_type richardson | chebyshev | preonly in pb_ksp_stationary.cpp, the
-// projected initial guess in pb_ksp_guess.cpp; struct pb_ksp and what they share in pb_ksp.hpp.
+// projected initial guess in pb_ksp_guess.cpp, -ksp_norm_type in pb_norm_type.cpp; struct pb_ksp
+// and what they share in pb_ksp.hpp.
 //
 // The CG iteration runs as 2 fused stencil passes + 2 one-block finalize kernels per iteration
 // (plus a plane-sized boundary kernel and, on several ranks, one halo exchange and two scalar
@@ -117,9 +118,10 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
     if (field_alloc(&k->w, vb) != hipSuccess || field_alloc(&k->z, vb) != hipSuccess)
       return fail(set_error(PB_ERR_ALLOC, "KSP work vectors: out of device memory"));
   }
-  // [1]: the folded iteration's second slot; behind them two doubles: the sums of M^-1 b a
-  // stored-z setup from a nonzero guess takes for its reference norm (guess_bsums)
-  if (hipMalloc(&k->d_st, 2 * sizeof(CgState) + 2 * sizeof(double)) != hipSuccess)
+  // [1]: the folded iteration's second slot; behind them four doubles: the sums of M^-1 b a
+  // stored-z setup from a nonzero guess takes for its reference norm (guess_bsums: t, t^2 for
+  // ||N(M^-1 b)||, and t.b, b for the natural norm's sqrt|b . N(M^-1 b)|)
+  if (hipMalloc(&k->d_st, 2 * sizeof(CgState) + 4 * sizeof(double)) != hipSuccess)
     return fail(set_error(PB_ERR_ALLOC, "KSP state: out of device memory"));
   if (k->opts.guess_type != PB_GUESS_NONE) {
     if (k->opts.guess_type != PB_GUESS_FISCHER)
@@ -157,20 +159,25 @@ static int guess_setup(pb_ksp* k, const double* b, const double* x0, double dinv
   int np = 0;
   if (k->stored_z()) {
     const double* bsums = nullptr;
-    if (ref != 1) {
-      // the reference norm ||N(M^-1 b)||: one more PC application, its sums kept aside
+    // unpreconditioned: the reference is ||b||, taken beside ||r_0|| by the residual kernel -- the
+    // PC application behind ||N(M^-1 b)|| disappears
+    const bool unp = k->norm_unp();
+    RrParts rr;
+    if (ref != 1 && !k->norm_none() && !unp) {
+      // the reference norm ||N(M^-1 b)|| (natural: sqrt|b . N(M^-1 b)|): one more PC application,
+      // its sums kept aside; -ksp_norm_type none tests nothing and needs no reference
       PB_TRY(pc_apply_dev(k, b, k->z, nullptr, &np));
       if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, b, k->d_st, &np));
       PB_TRY(cg_reduce_allreduce(ctx, ctx->d_partials, np, 4));
-      PB_HIP(hipMemcpyAsync(k->guess_bsums(), ctx->d_scalars, 2 * sizeof(double),
+      PB_HIP(hipMemcpyAsync(k->guess_bsums(), ctx->d_scalars, 4 * sizeof(double),
                             hipMemcpyDeviceToDevice, ctx->stream));
       bsums = k->guess_bsums();
     }
     PB_TRY(op_apply_raw(k->A, x0, k->w));
-    PB_TRY(launch_cg_guess_resid(g, b, k->w, k->r, k->pb[0], dinv, nullptr));
+    PB_TRY(launch_cg_guess_resid(g, b, k->w, k->r, k->pb[0], dinv, nullptr, unp ? &rr : nullptr));
     PB_TRY(pc_apply_dev(k, k->r, k->z, nullptr, &np));
     if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, k->r, k->d_st, &np));
-    return cg_finalize_guess(ctx, np, 4, bsums, ref, k->d_st, k->d_hist, k->h_done_dev);
+    return cg_finalize_guess(ctx, np, 4, bsums, ref, k->d_st, k->d_hist, k->h_done_dev, rr);
   }
   if (!fused_kind(k->A->kind)) {  // compact / assembled A with Jacobi / no PC
     PB_TRY(op_apply_raw(k->A, x0, k->w));
@@ -244,6 +251,7 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   st.nhist = k->nhist;
   st.pc = k->opts.pc_type;
   st.nullspace = k->opts.nullspace;
+  st.norm = k->norm();
   // PCJacobi stores the reciprocal of diag(P) (src/coefficients.f90:44-46 centre coefficient);
   // with SOR / MG the sums are taken over z = M^-1 r itself (dinv = 1)
   st.dinv = k->opts.pc_type == PB_PC_JACOBI ? 1.0 / k->P->cc : 1.0;
@@ -315,9 +323,11 @@ static int cg_begin(pb_ksp* k, const pb_vec* b, pb_vec* x, CgState& st) {
       PB_HIP(hipMemsetAsync(k->pb[0], 0, vb, ctx->stream));
     }
     int np = 0;
+    RrParts rr;  // unpreconditioned: ||r_0|| = ||b|| by a reduction pass of its own (setup only)
+    if (k->norm_unp()) PB_TRY(launch_cg_rr(g, r0, &rr));
     PB_TRY(pc_apply_dev(k, r0, k->z, nullptr, &np));
     if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, r0, k->d_st, &np));
-    PB_TRY(cg_finalize_init(ctx, np, k->d_st, k->d_hist, k->h_done_dev));
+    PB_TRY(cg_finalize_init(ctx, np, k->d_st, k->d_hist, k->h_done_dev, rr));
   } else {
     PB_TRY(launch_cg_init(g, b->d, x->d, k->r, k->pb[0], k->d_st, st.dinv, k->d_hist,
                           k->h_done_dev));
@@ -398,18 +408,22 @@ static int enqueue_pc_iteration(pb_ksp* k) {
   PB_TRY(cg_finalize_pass_a(ctx, np, k->d_st));
   const double* r_in = first ? k->b->d : k->r;
   const int rupd = tune("fft_rupd", 1);
-  if (k->fft && rupd && fftpc_fuses_r_update(k->fft)) {
+  // unpreconditioned norm: sum r^2 is taken where r is formed, in cg_pc_xr's registers -- the
+  // spectral PC's fused r update has no sum of its own and gives way to the unfused pair
+  RrParts rr;
+  const bool unp = k->norm_unp();
+  if (k->fft && rupd && fftpc_fuses_r_update(k->fft) && !unp) {
     // r = r_in - alpha w formed by the spectral PC's first pass as it loads r, x = x + alpha p
     // beside it (8 B/DoF and one vector pass fewer)
     const RUpdate ru{r_in, k->w, k->r, p, k->x->d, first, k->d_st};
     np = 0;
     PB_TRY(fftpc_apply(k->fft, k->r, k->z, &k->d_st->done, k->d_st, &np, &ru));
   } else {
-    PB_TRY(launch_cg_pc_xr(g, p, k->w, k->x->d, r_in, k->r, k->d_st, first));
+    PB_TRY(launch_cg_pc_xr(g, p, k->w, k->x->d, r_in, k->r, k->d_st, first, unp ? &rr : nullptr));
     PB_TRY(pc_apply_dev(k, k->r, k->z, &k->d_st->done, &np));
   }
   if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, k->r, k->d_st, &np));
-  return cg_finalize_stage2(ctx, np, k->d_st, k->d_hist, k->h_done_dev, k->host_iter);
+  return cg_finalize_stage2(ctx, np, k->d_st, k->d_hist, k->h_done_dev, k->host_iter, rr);
 }
 
 // the single-reduction iteration's two partial-sum regions (5 wide): iteration n of a batch
@@ -673,13 +687,17 @@ static int enqueue_iteration(pb_ksp* k, bool fold, bool fold_a) {
     nparts = nb1 + nb2;
   }
   PB_TRY(cg_finalize_pass_a(ctx, nparts, k->d_st));
+  // (unpreconditioned norm with a stored-z PC: pass B's own four sums of t = r - mu, kept in the
+  // second partial region, give sum r^2 to the stage below)
+  RrParts rr;
   PB_TRY(launch_cg_pass_b(g, s, p_new, p_prev, k->x->d, r, gp, k->d_st, k->d_hist,
-                          k->h_done_dev, i, k->defer_x, !k->stored_z(), ps));
+                          k->h_done_dev, i, k->defer_x, !k->stored_z(), ps,
+                          k->stored_z() && k->norm_unp() ? &rr : nullptr));
   if (k->stored_z()) {  // z = M^-1 r, then the residual sums over z
     int np = 0;
     PB_TRY(pc_apply_dev(k, r, k->z, &k->d_st->done, &np));
     if (np == 0) PB_TRY(launch_cg_pc_sums(g, k->z, r, k->d_st, &np));
-    PB_TRY(cg_finalize_stage2(ctx, np, k->d_st, k->d_hist, k->h_done_dev, i));
+    PB_TRY(cg_finalize_stage2(ctx, np, k->d_st, k->d_hist, k->h_done_dev, i, rr));
   }
   return PB_OK;
 }
@@ -703,6 +721,7 @@ int pb_ksp_iterate(pb_ksp* k, int64_t iters) {
   // (PB_CG_FOLD=0 keeps the separate finalize launches)
   const bool fold = C >= 2 && !k->rich() && fused_kind(k->A->kind) && !k->stored_z() &&
                     tune("cg_fold", 1) != 0;
+  const bool none = k->norm_none();
   int64_t n = 0;
   for (; n < iters && !k->stopped; ++n) {
     if (k->rich()) PB_TRY(enqueue_rich_iteration(k));
@@ -712,6 +731,7 @@ int pb_ksp_iterate(pb_ksp* k, int64_t iters) {
     // only the iterations the poll below waits for get an event (j = 0 mod C; folded j + 1): an
     // event record between two kernels costs the stream ~6 us of idle time (measured 5.9 us per
     // iteration with one record per iteration; profiles/r02/cg_gaps_*.txt)
+    if (none) continue;  // KSPConvergedSkip: no test to poll for; the caller's wait is the only one
     if (hi % C == (fold ? 1 : 0) % C)
       PB_HIP(hipEventRecord(k->ring[hi % R], ctx->stream));
     // lagged, rank-consistent poll: decide on the flag of iteration hi + 1 - C only (folded:
@@ -822,7 +842,7 @@ int pb_ksp_solve(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, doub
   if (k->opts.ksp_type == PB_KSP_PREONLY) return solve_preonly(k, b, x, res);
   if (k->opts.guess_type != PB_GUESS_NONE) return solve_projected(k, b, x, res, history, cap);
   PB_TRY(pb_ksp_begin(k, b, x));
-  PB_TRY(pb_ksp_iterate(k, k->opts.max_it + 2 * (int64_t)k->opts.check_every));
+  PB_TRY(pb_ksp_iterate(k, k->solve_iters()));
   return pb_ksp_end(k, res, history, cap);
 }
 

@@ -1197,12 +1197,44 @@ __global__ __launch_bounds__(256) void cg_boundary_kernel(const double* __restri
 // scalar logic (KSPSolve_CG + KSPConvergedDefault) on the device. mode bit 1 = reduce partials
 // into sums[], bit 2 = update the state from sums[] (split around the RCCL allreduce).
 // stage 0 = after init, 1 = after pass A (p.w), 2 = after pass B (residual sums), 3 = delta only.
+// the second partial region of -ksp_norm_type unpreconditioned with a stored-z PC (RrParts):
+// columns c0, c1 (c1 < 0: none) of nparts x width partials summed by the block's 256 threads in a
+// fixed order into out[0..1]
+__device__ __forceinline__ void rr_reduce(const RrParts& rr, int c0, int c1, double* out) {
+  __shared__ double red2[256][2];
+  double v0 = 0.0, v1 = 0.0;
+  for (int b = threadIdx.x; b < rr.nparts; b += 256) {
+    v0 += rr.parts[(int64_t)b * rr.width + c0];
+    if (c1 >= 0) v1 += rr.parts[(int64_t)b * rr.width + c1];
+  }
+  red2[threadIdx.x][0] = v0;
+  red2[threadIdx.x][1] = v1;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+      red2[threadIdx.x][0] += red2[threadIdx.x + off][0];
+      red2[threadIdx.x][1] += red2[threadIdx.x + off][1];
+    }
+    __syncthreads();
+  }
+  out[0] = red2[0][0];
+  out[1] = red2[0][1];
+}
+
+// rr.parts != nullptr (stages 0 and 2, width 4): this rank's sum r^2 joins the four as sums[4]
+// (mode bit 1) and travels in the same allreduce
 __global__ __launch_bounds__(256) void cg_finalize_kernel(const double* __restrict__ parts,
                                                           int nparts, int width, double* sums,
                                                           int mode, int stage, CgState* st,
                                                           double* hist, int* h_done,
-                                                          int64_t host_iter) {
+                                                          int64_t host_iter, RrParts rr) {
   double S[kMaxSums];
+  if ((mode & 1) && rr.parts) {
+    double q[2];
+    rr_reduce(rr, rr.width == 4 ? 2 : 0, rr.width == 4 ? 3 : -1, q);
+    // (pass B's sums: t = r - mu with the mean the state still holds, so t.r + mu r = r^2)
+    if (threadIdx.x == 0) sums[4] = rr.width == 4 ? q[0] + st->mu * q[1] : q[0];
+  }
   if ((mode & 1) && nparts > kFoldMaxParts) {
     // many partials (elementwise / multigrid kernels): 256-thread fixed-order tree
     __shared__ double red[256][kMaxSums];
@@ -1227,7 +1259,8 @@ __global__ __launch_bounds__(256) void cg_finalize_kernel(const double* __restri
       for (int s = 0; s < width; ++s) sums[s] = S[s];
   }
   if (!(mode & 2) || threadIdx.x != 0) return;
-  for (int s = 0; s < kMaxSums; ++s) S[s] = s < width ? sums[s] : 0.0;
+  const int ws = rr.parts ? 5 : width;
+  for (int s = 0; s < kMaxSums; ++s) S[s] = s < ws ? sums[s] : 0.0;
   if (stage == 0) cg_stage0(*st, S, hist, h_done);
   else if (stage == 1) cg_stage1(*st, S[0]);
   else if (stage == 2) cg_stage2(*st, S, hist, h_done, host_iter);
@@ -1237,21 +1270,25 @@ __global__ __launch_bounds__(256) void cg_finalize_kernel(const double* __restri
 
 static int cg_reduce_update(pb_ctx* ctx, int stage, int nparts, int width, CgState* st,
                             double* hist, int* h_done, int64_t host_iter,
-                            const double* parts = nullptr) {
+                            const double* parts = nullptr, const RrParts& rr = RrParts{}) {
   double* sums = ctx->d_scalars;
   if (!parts) parts = ctx->d_partials;
+  ScopedTimer tm(ctx, "cg_finalize");  // (with its allreduce on several ranks)
+  // (the PC's own partials must have stayed below the second region)
+  if (rr.parts && ((int64_t)nparts * width > ctx->partials_cap / 2 || width != 4))
+    return set_error(PB_ERR_UNSUPPORTED, "unpreconditioned norm: partial sums do not fit");
   if (!ctx->split) {
     hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts,
-                       nparts, width, sums, 3, stage, st, hist, h_done, host_iter);
+                       nparts, width, sums, 3, stage, st, hist, h_done, host_iter, rr);
     PB_HIP(hipGetLastError());
     return PB_OK;
   }
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts,
-                     nparts, width, sums, 1, stage, st, hist, h_done, host_iter);
+                     nparts, width, sums, 1, stage, st, hist, h_done, host_iter, rr);
   PB_HIP(hipGetLastError());
-  PB_TRY(allreduce_device(ctx, sums, width));
+  PB_TRY(allreduce_device(ctx, sums, rr.parts ? 5 : width));
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts,
-                     nparts, width, sums, 2, stage, st, hist, h_done, host_iter);
+                     nparts, width, sums, 2, stage, st, hist, h_done, host_iter, rr);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
@@ -1293,20 +1330,21 @@ int launch_cg_guess_init(pb_grid* g, const Star& s, const double* x0, const doub
 // skip = false: the setup's launch (the state's done flag is not valid yet)
 int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double* q,
                        const double* b, double* x_out, double* r_out, const StencilPlanes& gp,
-                       const CgState* st, double scale, bool sums, bool skip, int* nparts) {
+                       const CgState* st, double scale, bool sums, bool skip, int* nparts,
+                       int part_off) {
   ScopedTimer tm(g->ctx, q ? "rich_update" : "rich_resid");
   const int* sk = skip ? &st->done : nullptr;
   *nparts = 0;
   if (q) {
     const RichLoad ld{x, q, st, scale};
     if (sums)
-      return launch_any(g, s, ld, gp, RichEpi<true, true>{x_out, r_out, b, st}, sk, PLANES_ALL, 0,
-                        nparts);
+      return launch_any(g, s, ld, gp, RichEpi<true, true>{x_out, r_out, b, st}, sk, PLANES_ALL,
+                        part_off, nparts);
     return launch_any(g, s, ld, gp, RichEpi<true, false>{x_out, r_out, b, st}, sk);
   }
   if (sums)
     return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, true>{nullptr, r_out, b, st}, sk,
-                      PLANES_ALL, 0, nparts);
+                      PLANES_ALL, part_off, nparts);
   return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, false>{nullptr, r_out, b, st}, sk);
 }
 
@@ -1315,13 +1353,13 @@ int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double*
 int launch_cheb_update(pb_grid* g, const Star& s, const double* y, const double* ym1,
                        const double* q, const double* b, double* y_out, double* r_out,
                        const StencilPlanes& gp, const CgState* st, double scale, bool sums,
-                       int* nparts) {
+                       int* nparts, int part_off) {
   ScopedTimer tm(g->ctx, "cheb_update");
   *nparts = 0;
   const ChebLoad ld{y, ym1, q, st, scale};
   if (sums)
     return launch_any(g, s, ld, gp, RichEpi<true, true>{y_out, r_out, b, st}, &st->done,
-                      PLANES_ALL, 0, nparts);
+                      PLANES_ALL, part_off, nparts);
   return launch_any(g, s, ld, gp, RichEpi<true, false>{y_out, r_out, b, st}, &st->done);
 }
 
@@ -1334,8 +1372,15 @@ __global__ __launch_bounds__(256) void cg_guess_finalize_kernel(const double* __
                                                                 double* sums, int mode,
                                                                 const double* bsums, int ref,
                                                                 CgState* st, double* hist,
-                                                                int* h_done) {
+                                                                int* h_done, RrParts rr) {
   constexpr int W = 6;
+  // rr (unpreconditioned norm, stored-z PC; width 4): sum r^2 and sum b^2 of the residual kernel
+  // join the four as sums[4..5] -- ||r_0|| and the reference ||b||, no PC application behind it
+  if ((mode & 1) && rr.parts) {
+    double q[2];
+    rr_reduce(rr, 0, 1, q);
+    if (threadIdx.x == 0) sums[4] = q[0], sums[5] = q[1];
+  }
   if (mode & 1) {
     __shared__ double red[256][W];
     for (int s = 0; s < width; ++s) {
@@ -1354,38 +1399,49 @@ __global__ __launch_bounds__(256) void cg_guess_finalize_kernel(const double* __
   }
   if (!(mode & 2) || threadIdx.x != 0) return;
   double S[kMaxSums];
-  for (int s = 0; s < kMaxSums; ++s) S[s] = s < 4 ? sums[s] : 0.0;
+  for (int s = 0; s < kMaxSums; ++s) S[s] = s < (rr.parts ? 5 : 4) ? sums[s] : 0.0;
   double bnorm = 0.0;
-  if (ref != REF_INITIAL) {
+  if (ref != REF_INITIAL && st->norm != PB_KSP_NORM_NONE) {
     const double* bs = bsums ? bsums : sums + 4;
-    double zz = bs[1];
-    if (st->nullspace) {
-      const double delta = bs[0] / st->ntot;
-      zz = bs[1] - st->ntot * delta * delta;
+    const double delta = st->nullspace ? bs[0] / st->ntot : 0.0;
+    if (st->norm == PB_KSP_NORM_PRECONDITIONED) {
+      double zz = bs[1];
+      if (st->nullspace) zz = bs[1] - st->ntot * delta * delta;
+      bnorm = norm_from_sq(zz);
+    } else if (st->norm == PB_KSP_NORM_NATURAL) {
+      // sqrt|b . N(M^-1 b)|. bsums: the four sums of t = M^-1 b (t, t^2, t.b, b); the fused
+      // setup's pair: sb = dinv b, so b . sb = sum sb^2 / dinv and sum b = sum sb / dinv
+      const double bz = bsums ? bs[2] - delta * bs[3] : (bs[1] - delta * bs[0]) / st->dinv;
+      bnorm = sqrt(fabs(bz));
+    } else {
+      // ||b||_2, no PC application: sum b^2 = sum sb^2 / dinv^2 (Jacobi / no PC), or taken beside
+      // sum r^2 (rr)
+      bnorm = norm_from_sq(rr.parts ? sums[5] : bs[1] / (st->dinv * st->dinv));
     }
-    bnorm = norm_from_sq(zz);
   }
   cg_stage0(*st, S, hist, h_done, ref, bnorm);
 }
 
 int cg_finalize_guess(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
-                      CgState* st, double* hist, int* h_done) {
+                      CgState* st, double* hist, int* h_done, const RrParts& rr) {
   double* sums = ctx->d_scalars;
+  if (rr.parts && ((int64_t)nparts * width > ctx->partials_cap / 2 || width != 4))
+    return set_error(PB_ERR_UNSUPPORTED, "unpreconditioned norm: partial sums do not fit");
   if (!ctx->split) {
     hipLaunchKernelGGL(cg_guess_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                        (const double*)ctx->d_partials, nparts, width, sums, 3, bsums, ref, st, hist,
-                       h_done);
+                       h_done, rr);
     PB_HIP(hipGetLastError());
     return PB_OK;
   }
   hipLaunchKernelGGL(cg_guess_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      (const double*)ctx->d_partials, nparts, width, sums, 1, bsums, ref, st, hist,
-                     h_done);
+                     h_done, rr);
   PB_HIP(hipGetLastError());
-  PB_TRY(allreduce_device(ctx, sums, width));
+  PB_TRY(allreduce_device(ctx, sums, rr.parts ? 6 : width));
   hipLaunchKernelGGL(cg_guess_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      (const double*)ctx->d_partials, nparts, width, sums, 2, bsums, ref, st, hist,
-                     h_done);
+                     h_done, rr);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
@@ -1473,7 +1529,7 @@ int cg_reduce_allreduce(pb_ctx* ctx, int nparts, int width, bool b_region) {
 int cg_reduce_allreduce(pb_ctx* ctx, const double* parts, int nparts, int width) {
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts, width,
                      ctx->d_scalars, 1, 0, (CgState*)nullptr, (double*)nullptr, (int*)nullptr,
-                     (int64_t)0);
+                     (int64_t)0, RrParts{});
   PB_HIP(hipGetLastError());
   return allreduce_device(ctx, ctx->d_scalars, width);
 }
@@ -1483,13 +1539,14 @@ int cg_stage2_from_sums(pb_ctx* ctx, int width, CgState* st, double* hist, int* 
                         int64_t host_iter) {
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      (const double*)nullptr, 0, width, ctx->d_scalars, 2, 2, st, hist, h_done,
-                     host_iter);
+                     host_iter, RrParts{});
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done) {
-  return cg_reduce_update(ctx, 0, nparts, 4, st, hist, h_done, -1);
+int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
+                     const RrParts& rr) {
+  return cg_reduce_update(ctx, 0, nparts, 4, st, hist, h_done, -1, nullptr, rr);
 }
 
 int cg_finalize_pass_a(pb_ctx* ctx, int nparts, CgState* st) {
@@ -1497,8 +1554,8 @@ int cg_finalize_pass_a(pb_ctx* ctx, int nparts, CgState* st) {
 }
 
 int cg_finalize_stage2(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
-                       int64_t host_iter) {
-  return cg_reduce_update(ctx, 2, nparts, 4, st, hist, h_done, host_iter);
+                       int64_t host_iter, const RrParts& rr) {
+  return cg_reduce_update(ctx, 2, nparts, 4, st, hist, h_done, host_iter, nullptr, rr);
 }
 
 // pass B variants by the x-update position; fold.stage = 1: stage 1 in the prologue (partials
@@ -1508,9 +1565,9 @@ int cg_finalize_stage2(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* 
 template <int XU, bool PST>
 static int pass_b_one(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
                       double* x, double* r, const StencilPlanes& gp, CgState* st, const Fold& f,
-                      const PStore& ps, int* nparts) {
+                      const PStore& ps, int* nparts, int part_off = 0) {
   const int* skip = f.stage ? nullptr : &st->done;
-  const int off = f.stage ? (int)fold_parts_b_off(g->ctx) : 0;
+  const int off = f.stage ? (int)fold_parts_b_off(g->ctx) : part_off;
   PassB<XU, PST> ep{x, r, p_prev[0], XU == 3 ? p_prev[1] : nullptr, XU == 3 ? p_prev[2] : nullptr,
                     st, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if constexpr (PST) {
@@ -1527,37 +1584,45 @@ static int pass_b_one(pb_grid* g, const Star& s, const double* p, const double* 
 template <bool PST>
 static int pass_b_pick(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
                        double* x, double* r, const StencilPlanes& gp, CgState* st,
-                       int64_t host_iter, int defer, const Fold& f, const PStore& ps, int* nparts) {
+                       int64_t host_iter, int defer, const Fold& f, const PStore& ps, int* nparts,
+                       int part_off) {
   if (defer == 0) {
     ScopedTimer tm(g->ctx, "cg_pass_b");
-    return pass_b_one<2, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts);
+    return pass_b_one<2, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
   }
   if (host_iter % defer != defer - 1) {
     ScopedTimer tm(g->ctx, "cg_pass_b_even");
-    return pass_b_one<0, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts);
+    return pass_b_one<0, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
   }
   if (defer == 2) {
     ScopedTimer tm(g->ctx, "cg_pass_b_odd");
-    return pass_b_one<1, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts);
+    return pass_b_one<1, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
   }
   ScopedTimer tm(g->ctx, "cg_pass_b_x4");
-  return pass_b_one<3, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts);
+  return pass_b_one<3, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
 }
 
 static int pass_b_launch(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
                          double* x, double* r, const StencilPlanes& gp, CgState* st,
                          int64_t host_iter, int defer, const Fold& f, const PStore& ps,
-                         int* nparts) {
+                         int* nparts, int part_off = 0) {
   if (ps.r_out)
-    return pass_b_pick<true>(g, s, p, p_prev, x, r, gp, st, host_iter, defer, f, ps, nparts);
-  return pass_b_pick<false>(g, s, p, p_prev, x, r, gp, st, host_iter, defer, f, ps, nparts);
+    return pass_b_pick<true>(g, s, p, p_prev, x, r, gp, st, host_iter, defer, f, ps, nparts,
+                             part_off);
+  return pass_b_pick<false>(g, s, p, p_prev, x, r, gp, st, host_iter, defer, f, ps, nparts,
+                            part_off);
 }
 
 int launch_cg_pass_b(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
                      double* x, double* r, const StencilPlanes& gp, CgState* st, double* hist,
-                     int* h_done, int64_t host_iter, int defer, bool finalize, const PStore& ps) {
+                     int* h_done, int64_t host_iter, int defer, bool finalize, const PStore& ps,
+                     RrParts* rr) {
   int nparts = 0;
-  PB_TRY(pass_b_launch(g, s, p, p_prev, x, r, gp, st, host_iter, defer, Fold{}, ps, &nparts));
+  // rr (unpreconditioned norm, stored-z PC): the four sums of t = r - mu this pass takes anyway
+  // go to the second region, where the PC's sums do not overwrite them (sum r^2 = t.r + mu r)
+  const int off = rr ? rr_part_off(g->ctx, 4) : 0;
+  PB_TRY(pass_b_launch(g, s, p, p_prev, x, r, gp, st, host_iter, defer, Fold{}, ps, &nparts, off));
+  if (rr) *rr = RrParts{rr_region(g->ctx), nparts, 4};
   if (!finalize) return PB_OK;  // preconditioned path: the sums come from z = M^-1 r later
   return cg_reduce_update(g->ctx, 2, nparts, 4, st, hist, h_done, host_iter);
 }
@@ -1583,7 +1648,7 @@ int cg_fold_tail(pb_ctx* ctx, int nparts_b, CgState* st2, double* hist, int* h_d
   // split grids: pass B's sums are already reduced and allreduced into d_scalars (mode 2 only)
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      ctx->d_partials + fold_parts_b_off(ctx) * 4, nparts_b, 4, ctx->d_scalars,
-                     ctx->split ? 2 : 3, 2, st2 + 1, hist, h_done, host_iter);
+                     ctx->split ? 2 : 3, 2, st2 + 1, hist, h_done, host_iter, RrParts{});
   PB_HIP(hipGetLastError());
   PB_HIP(hipMemcpyAsync(st2, st2 + 1, sizeof(CgState), hipMemcpyDeviceToDevice, ctx->stream));
   return PB_OK;

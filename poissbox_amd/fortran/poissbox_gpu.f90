@@ -90,6 +90,10 @@ module poissbox_gpu
   end type pb_ksp_result
 
   integer(c_int), parameter, public :: PB_OP_STAR7 = 0, PB_OP_COMPACT = 1, PB_OP_ASSEMBLED27 = 2
+  !! -ksp_norm_type (pb_ksp_norm_type: PETSc's KSPNormType values)
+  integer(c_int), parameter, public :: PB_KSP_NORM_DEFAULT = -1, PB_KSP_NORM_NONE = 0
+  integer(c_int), parameter, public :: PB_KSP_NORM_PRECONDITIONED = 1
+  integer(c_int), parameter, public :: PB_KSP_NORM_UNPRECONDITIONED = 2, PB_KSP_NORM_NATURAL = 3
 
   type(c_ptr), save :: g_ctx = c_null_ptr  ! one context per process (one GPU), like PETSC_COMM_WORLD
 
@@ -115,6 +119,10 @@ module poissbox_gpu
   ! -pc_type mg: the level smoother (-mg_levels_ksp_type, -mg_levels_pc_type, ...)
   public :: c_pb_pc_mg_opts_default, c_pb_pc_mg_opts_parse, c_pb_ksp_pc_mg_set_opts
   public :: c_pb_ksp_pc_mg_get_opts, c_pb_solve_mg
+  ! -ksp_norm_type (≙ KSPSetNormType / KSPGetNormType) and the KSP object it is set on
+  public :: c_pb_ksp_norm_type_parse, c_pb_ksp_set_norm_type, c_pb_ksp_get_norm_type
+  public :: c_pb_ksp_opts_default, c_pb_ksp_opts_parse
+  public :: c_pb_ksp_create, c_pb_ksp_solve, c_pb_ksp_destroy
 
   interface PoissboxAllreduceSum  ! ≙ MPI_Allreduce(..., MPI_SUM, MPI_COMM_WORLD)
      module procedure allreduce_sum_int, allreduce_sum_real
@@ -499,6 +507,42 @@ module poissbox_gpu
        type(pb_ksp_result) :: res
        integer(c_int64_t), value :: cap
      end function
+     integer(c_int) function c_pb_ksp_norm_type_parse(norm_type, argc, argv) &
+          bind(C, name="pb_ksp_norm_type_parse")
+       import :: c_int, c_ptr
+       integer(c_int) :: norm_type
+       integer(c_int), value :: argc
+       type(c_ptr), dimension(*) :: argv
+     end function
+     integer(c_int) function c_pb_ksp_set_norm_type(ksp, norm_type) &
+          bind(C, name="pb_ksp_set_norm_type")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp
+       integer(c_int), value :: norm_type
+     end function
+     !! norm_set: as set (PB_KSP_NORM_DEFAULT after create); norm_effective: the one in force
+     integer(c_int) function c_pb_ksp_get_norm_type(ksp, norm_set, norm_effective) &
+          bind(C, name="pb_ksp_get_norm_type")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp
+       integer(c_int) :: norm_set, norm_effective
+     end function
+     integer(c_int) function c_pb_ksp_create(A, P, o, ksp) bind(C, name="pb_ksp_create")
+       import :: c_int, c_ptr, pb_ksp_opts
+       type(c_ptr), value :: A, P
+       type(pb_ksp_opts) :: o
+       type(c_ptr) :: ksp
+     end function
+     integer(c_int) function c_pb_ksp_solve(ksp, b, x, res, hist, cap) bind(C, name="pb_ksp_solve")
+       import :: c_int, c_ptr, c_int64_t, pb_ksp_result
+       type(c_ptr), value :: ksp, b, x, hist
+       type(pb_ksp_result) :: res
+       integer(c_int64_t), value :: cap
+     end function
+     integer(c_int) function c_pb_ksp_destroy(ksp) bind(C, name="pb_ksp_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp
+     end function
      integer(c_int) function c_pb_ksp_chebyshev_get_eigenvalues(ksp, emin, emax, estimated) &
           bind(C, name="pb_ksp_chebyshev_get_eigenvalues")
        import :: c_int, c_ptr, c_double
@@ -756,6 +800,8 @@ contains
     type(pb_pc_mg_opts) :: mo
     type(pb_ksp_result) :: res
     integer :: nargs, i, l, lmax
+    integer(c_int) :: norm_type, ierr2
+    type(c_ptr) :: ksp
     character(len=:), allocatable, target :: args(:)
     type(c_ptr), allocatable :: argv(:)
 
@@ -778,6 +824,8 @@ contains
     if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_parse(co, int(nargs, c_int), argv)
     if (ierr == 0) ierr = c_pb_pc_mg_opts_default(mo)
     if (ierr == 0) ierr = c_pb_pc_mg_opts_parse(mo, int(nargs, c_int), argv)
+    norm_type = PB_KSP_NORM_DEFAULT
+    if (ierr == 0) ierr = c_pb_ksp_norm_type_parse(norm_type, int(nargs, c_int), argv)
     if (ierr /= 0) then
        call check(ierr, "KSPSetFromOptions")
        return
@@ -785,7 +833,22 @@ contains
     if (c_associated(A%h, P%h) .eqv. .false.) print *, "Setting nullspace on A"
     ! (the Chebyshev settings are read by a KSP of that type only)
     ! (-pc_type mg under another KSP type takes its level smoother, -mg_levels_*, instead)
-    if (o%pc_type == 3 .and. o%ksp_type /= 3) then
+    ! (-ksp_norm_type lives on the KSP object, as KSPSetNormType: a KSP for this one solve)
+    if (norm_type /= PB_KSP_NORM_DEFAULT) then
+       ksp = c_null_ptr
+       ierr = c_pb_ksp_create(A%h, P%h, o, ksp)
+       if (ierr == 0) then
+          if (o%ksp_type == 3) then
+             ierr = c_pb_ksp_chebyshev_set_opts(ksp, co)
+          else if (o%pc_type == 3) then
+             ierr = c_pb_ksp_pc_mg_set_opts(ksp, mo)
+          end if
+          if (ierr == 0) ierr = c_pb_ksp_set_norm_type(ksp, norm_type)
+          if (ierr == 0) ierr = c_pb_ksp_solve(ksp, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
+          ierr2 = c_pb_ksp_destroy(ksp)  ! (a successful destroy leaves the last error's text)
+          if (ierr == 0) ierr = ierr2
+       end if
+    else if (o%pc_type == 3 .and. o%ksp_type /= 3) then
        ierr = c_pb_solve_mg(A%h, P%h, o, mo, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
     else
        ierr = c_pb_solve_chebyshev(A%h, P%h, o, co, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
