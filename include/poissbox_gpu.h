@@ -250,9 +250,29 @@ int pb_vec_get_ownership_range(const pb_vec* v, int64_t* first, int64_t* next);
  *    b and x must be distinct (PB_ERR_ARG). Works with every operator, PC, initial_guess_nonzero,
  *    guess_type fischer and the split form, as PB_KSP_RICHARDSON does; every solve and every
  *    pb_ksp_begin restarts rho.
+ *  PB_KSP_FGMRES (PETSc KSPSolve_FGMRES / KSPFGMRESCycle: restarted flexible GMRES, classical
+ *    Gram-Schmidt, right preconditioning only): the one type here that tolerates a preconditioner
+ *    that is not one fixed symmetric linear operator. Step k of a cycle stores z_k = N(M^-1 v_k),
+ *    forms w = A z_k, h_j = <w, v_j> (j <= k), w -= sum h_j v_j, h_(k+1,k) = ||w||, rotates the
+ *    column with the stored Givens rotations and forms the new one; |g_(k+1)| -- the true residual
+ *    norm ||b - A x|| in exact arithmetic -- is the iteration's norm, logged and tested by the
+ *    default test. After `restart` steps (pb_ksp_fgmres_opts, default 30) x += sum y_j z_j from
+ *    the triangular solve, r = b - A x is recomputed, and its norm starts the next cycle: it is
+ *    tested at the same iteration count and not logged as an extra entry (nhist = its + 1;
+ *    entry k is the estimate after k iterations). max_it reached inside a cycle builds the
+ *    solution from the partial cycle: PB_KSP_DIVERGED_ITS. The norm type is unpreconditioned (the
+ *    default here) or none; the reference norm with a nonzero guess is the one
+ *    -ksp_norm_type unpreconditioned gives PB_KSP_CG (||b||, and the two
+ *    converged_use_*_initial_residual_norm switches). b and x must be distinct. guess_type
+ *    fischer is PB_ERR_UNSUPPORTED with it. The KSP keeps up to 2 restart fields beside its
+ *    work vectors (allocated in chunks as a cycle first reaches them). On the
+ *    7-point operator with Jacobi / no PC (one rank) a step starts with one engine pass that forms
+ *    and stores v_k and z_k and writes A z_k; there the mean of z_k is taken from the sum of the
+ *    unnormalised direction (equal in exact arithmetic to the mean over z_k).
  * cg_single_reduction is a CG option: the other types ignore it. */
 enum pb_ksp_type {
-  PB_KSP_CG = 0, PB_KSP_PREONLY = 1, PB_KSP_RICHARDSON = 2, PB_KSP_CHEBYSHEV = 3
+  PB_KSP_CG = 0, PB_KSP_PREONLY = 1, PB_KSP_RICHARDSON = 2, PB_KSP_CHEBYSHEV = 3,
+  PB_KSP_FGMRES = 4
 };
 /* seed of the noise vector (pb_vec_set_random) the Chebyshev eigenvalue estimate starts from */
 #define PB_CHEBYSHEV_ESTEIG_SEED 20240607ULL
@@ -267,14 +287,18 @@ enum pb_ksp_reason {
   PB_KSP_ITERATING = 0, PB_KSP_CONVERGED_RTOL = 2, PB_KSP_CONVERGED_ATOL = 3,
   PB_KSP_CONVERGED_ITS = 4, PB_KSP_DIVERGED_ITS = -3, PB_KSP_DIVERGED_DTOL = -4,
   PB_KSP_DIVERGED_INDEFINITE_PC = -8, PB_KSP_DIVERGED_NANORINF = -9,
-  PB_KSP_DIVERGED_INDEFINITE_MAT = -10
+  PB_KSP_DIVERGED_INDEFINITE_MAT = -10,
+  /* PB_KSP_FGMRES: the new direction vanished (||w|| below the happy-breakdown bound) -- with
+   * -ksp_norm_type none that ends the solve as converged, otherwise the default test sees the
+   * estimate 0 first and DIVERGED_BREAKDOWN is left for a test that still gives nothing */
+  PB_KSP_DIVERGED_BREAKDOWN = -5, PB_KSP_CONVERGED_HAPPY_BREAKDOWN = 7
 };
 typedef struct {
   double rtol;       /* -ksp_rtol   (PETSc default 1e-5)  */
   double atol;       /* -ksp_atol   (1e-50)               */
   double dtol;       /* -ksp_divtol (1e5)                 */
   int64_t max_it;    /* -ksp_max_it (10000)               */
-  int ksp_type;      /* -ksp_type cg|preonly|richardson|chebyshev */
+  int ksp_type;      /* -ksp_type cg|preonly|richardson|chebyshev|fgmres */
   int pc_type;       /* -pc_type none|jacobi|sor|mg       */
   int nullspace;     /* constant null space (src/poissbox.f90:285-291), default 1 */
   int monitor;       /* -ksp_monitor: print ||z_k|| per iteration after the solve (rank 0) */
@@ -360,6 +384,18 @@ typedef struct {
   double levels_eigenvalues[2];   /* -mg_levels_ksp_chebyshev_eigenvalues emin,emax; 0,0: derive */
   double levels_esteig[4];        /* -mg_levels_ksp_chebyshev_esteig a,b,c,d (0, 0.1, 0, 1.1) */
 } pb_pc_mg_opts;
+/* The settings of PB_KSP_FGMRES (PETSc KSPGMRESSetRestart, KSPGMRESSetHapTol,
+ * KSPGMRESSetCGSRefinementType): a struct of their own, set on the KSP after pb_ksp_create
+ * (pb_ksp_fgmres_set_opts), as pb_ksp_chebyshev_opts is. */
+enum pb_fgmres_refine { PB_FGMRES_REFINE_NEVER = 0, PB_FGMRES_REFINE_ALWAYS = 2 };
+typedef struct {
+  int restart;        /* -ksp_gmres_restart: steps per cycle, 1..64 (else PB_ERR_ARG), default 30 */
+  double haptol;      /* -ksp_gmres_haptol: happy-breakdown tolerance, finite and > 0 (1e-30) */
+  int cgs_refinement; /* -ksp_gmres_cgs_refinement_type refine_never|refine_always
+                         (PB_FGMRES_REFINE_*; refine_ifneeded: PB_ERR_UNSUPPORTED). refine_always
+                         runs the multi-dot / multi-axpy pair twice per step and adds the second
+                         coefficients into the Hessenberg column */
+} pb_ksp_fgmres_opts;
 typedef struct {
   int reason;
   int64_t its;
@@ -370,7 +406,8 @@ typedef struct {
                         after a breakdown exit (beta = 0, indefinite PC / matrix) */
 } pb_ksp_result;
 int pb_ksp_opts_default(pb_ksp_opts* opts);
-/* Parses PETSc-style options (-ksp_type cg|preonly|richardson|chebyshev, -ksp_richardson_scale,
+/* Parses PETSc-style options (-ksp_type cg|preonly|richardson|chebyshev|fgmres,
+ * -ksp_richardson_scale,
  * -pc_type,
  * -ksp_rtol, -ksp_atol, -ksp_divtol, -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
  * -pc_sor_omega, and the PetscOptionsBool flags -ksp_cg_single_reduction,
@@ -407,7 +444,8 @@ int pb_ksp_destroy(pb_ksp* ksp);
  * pb_ksp_result.rnorm, rnorm0). z = N(M^-1 r) and the iteration (alpha, beta, p, x, r) are the same
  * under every type; the values are PETSc's KSPNormType.
  *   preconditioned (the default of cg / richardson / chebyshev): ||z_i||_2; from a nonzero guess the
- *     reference is ||N(M^-1 b)||
+ *     reference is ||N(M^-1 b)||. PB_KSP_FGMRES is right-preconditioned: its default is
+ *     unpreconditioned, and preconditioned / natural are PB_ERR_UNSUPPORTED on it
  *   unpreconditioned: ||r_i||_2 = ||b - A x_i||_2, the plain 2-norm (no mean shift); reference ||b||_2
  *   natural (cg only): sqrt(|r_i . z_i|); reference sqrt(|b . N(M^-1 b)|)
  *   none: no norm and no test (KSPConvergedSkip): the solve runs max_it iterations and ends with
@@ -428,12 +466,13 @@ enum pb_ksp_norm_type {
  * PB_ERR_UNSUPPORTED and leaves *type as it was. */
 int pb_ksp_norm_type_parse(int* type, int argc, const char* const* argv);
 /* ≙ KSPSetNormType. PB_ERR_ARG for a value outside the enum; PB_ERR_UNSUPPORTED for natural on
- * richardson / chebyshev (as PETSc refuses it) and for anything but default / none on preonly;
+ * richardson / chebyshev (as PETSc refuses it), for preconditioned / natural on fgmres and for
+ * anything but default / none on preonly;
  * PB_ERR_STATE between pb_ksp_begin and pb_ksp_end. An error leaves the KSP as it was. */
 int pb_ksp_set_norm_type(pb_ksp* ksp, int type);
 /* ≙ KSPGetNormType. *set: the value as set (PB_KSP_NORM_DEFAULT after create); *effective: the one
- * in force (default: preconditioned for cg / richardson / chebyshev, none for preonly). Either
- * may be NULL. */
+ * in force (default: preconditioned for cg / richardson / chebyshev, unpreconditioned for fgmres,
+ * none for preonly). Either may be NULL. */
 int pb_ksp_get_norm_type(const pb_ksp* ksp, int* set, int* effective);
 /* -ksp_chebyshev_eigenvalues emin,emax, -ksp_chebyshev_esteig a,b,c,d,
  * -ksp_chebyshev_esteig_steps n, -ksp_chebyshev_esteig_noisy [bool] from the same argument list
@@ -447,6 +486,22 @@ int pb_ksp_chebyshev_set_opts(pb_ksp* ksp, const pb_ksp_chebyshev_opts* opts);
 int pb_solve_chebyshev(pb_op* A, pb_op* P, const pb_ksp_opts* opts,
                        const pb_ksp_chebyshev_opts* cheb, const pb_vec* b, pb_vec* x,
                        pb_ksp_result* res, double* history, int64_t history_cap);
+/* -ksp_gmres_restart n, -ksp_gmres_haptol h, -ksp_gmres_cgs_refinement_type <type>,
+ * -ksp_gmres_classicalgramschmidt (no effect: it is the only orthogonalisation),
+ * -ksp_gmres_modifiedgramschmidt [bool] (PB_ERR_UNSUPPORTED when true) and -ksp_gmres_preallocate
+ * (accepted: the basis is allocated in chunks whatever it says) from the same argument list as
+ * pb_ksp_opts_parse, which skips them; other options are ignored, an option that is the last
+ * token without its value is skipped, and an error leaves *opts as it was. */
+int pb_ksp_fgmres_opts_default(pb_ksp_fgmres_opts* opts);
+int pb_ksp_fgmres_opts_parse(pb_ksp_fgmres_opts* opts, int argc, const char* const* argv);
+/* Sets them on a PB_KSP_FGMRES KSP (PB_ERR_STATE on another type or between pb_ksp_begin and
+ * pb_ksp_end; PB_ERR_ARG / PB_ERR_UNSUPPORTED for invalid values, which leave the KSP as it was) */
+int pb_ksp_fgmres_set_opts(pb_ksp* ksp, const pb_ksp_fgmres_opts* opts);
+int pb_ksp_fgmres_get_opts(const pb_ksp* ksp, pb_ksp_fgmres_opts* opts);
+/* pb_solve with these settings (fg may be NULL: the defaults) */
+int pb_solve_fgmres(pb_op* A, pb_op* P, const pb_ksp_opts* opts, const pb_ksp_fgmres_opts* fg,
+                    const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
+                    int64_t history_cap);
 /* -mg_levels_ksp_type, -mg_levels_pc_type, -mg_levels_ksp_max_it,
  * -mg_levels_ksp_richardson_scale, -mg_levels_ksp_chebyshev_eigenvalues emin,emax and
  * -mg_levels_ksp_chebyshev_esteig a,b,c,d from the same argument list as pb_ksp_opts_parse (which

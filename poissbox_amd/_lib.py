@@ -40,6 +40,10 @@ class KspChebyshevOpts(C.Structure):
     _fields_ = [("emin", c_d), ("emax", c_d), ("esteig", c_d * 4), ("esteig_steps", C.c_int)]
 
 
+class KspFgmresOpts(C.Structure):
+    _fields_ = [("restart", C.c_int), ("haptol", c_d), ("cgs_refinement", C.c_int)]
+
+
 class PcMgOpts(C.Structure):
     _fields_ = [("levels_ksp_type", C.c_int), ("levels_pc_type", C.c_int),
                 ("levels_ksp_max_it", C.c_int), ("levels_richardson_scale", c_d),
@@ -134,6 +138,12 @@ _SIGS = {
     "pb_solve_chebyshev": [c_p, c_p, C.POINTER(KspOpts), C.POINTER(KspChebyshevOpts), c_p, c_p,
                            C.POINTER(KspResult), P_d, c_i64],
     "pb_ksp_chebyshev_get_eigenvalues": [c_p, P_d, P_d, C.POINTER(C.c_int)],
+    "pb_ksp_fgmres_opts_default": [C.POINTER(KspFgmresOpts)],
+    "pb_ksp_fgmres_opts_parse": [C.POINTER(KspFgmresOpts), C.c_int, C.POINTER(C.c_char_p)],
+    "pb_ksp_fgmres_set_opts": [c_p, C.POINTER(KspFgmresOpts)],
+    "pb_ksp_fgmres_get_opts": [c_p, C.POINTER(KspFgmresOpts)],
+    "pb_solve_fgmres": [c_p, c_p, C.POINTER(KspOpts), C.POINTER(KspFgmresOpts), c_p, c_p,
+                        C.POINTER(KspResult), P_d, c_i64],
     "pb_pc_mg_opts_default": [C.POINTER(PcMgOpts)],
     "pb_pc_mg_opts_parse": [C.POINTER(PcMgOpts), C.c_int, C.POINTER(C.c_char_p)],
     "pb_ksp_pc_mg_set_opts": [c_p, C.POINTER(PcMgOpts)],

@@ -26,7 +26,10 @@ PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
 # x += scale M^-1 (b - A x) (ksp_options(richardson_scale=...) or -ksp_richardson_scale)
 # chebyshev = the accelerated stationary iteration for a spectrum of M^-1 A in [emin, emax]
 # (-ksp_chebyshev_eigenvalues emin,emax; estimated when not given: KSP.chebyshev_eigenvalues())
-KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV = 0, 1, 2, 3
+# fgmres = restarted flexible GMRES (right-preconditioned: the tested number is ||b - A x||;
+# -ksp_gmres_restart, -ksp_gmres_haptol, -ksp_gmres_cgs_refinement_type: pb_ksp_fgmres_opts)
+KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV, KSP_FGMRES = 0, 1, 2, 3, 4
+FGMRES_REFINE_NEVER, FGMRES_REFINE_ALWAYS = 0, 2
 # -mg_levels_ksp_type / -mg_levels_pc_type: the level smoother of -pc_type mg (pb_pc_mg_opts)
 MG_LEVELS_RICHARDSON, MG_LEVELS_CHEBYSHEV = 0, 1
 # pb_ksp_norm_type (PETSc's KSPNormType values)
@@ -37,7 +40,8 @@ MG_LEVELS_SOR, MG_LEVELS_JACOBI = 0, 1
 REASONS = {0: "CONVERGED_ITERATING", 2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL",
            4: "CONVERGED_ITS", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",
            -8: "DIVERGED_INDEFINITE_PC", -9: "DIVERGED_NANORINF",
-           -10: "DIVERGED_INDEFINITE_MAT"}
+           -10: "DIVERGED_INDEFINITE_MAT", -5: "DIVERGED_BREAKDOWN",
+           7: "CONVERGED_HAPPY_BREAKDOWN"}
 
 
 def _i64_3(v):
@@ -389,7 +393,9 @@ class KspOptions(L.KspOpts):
     mg_levels_ksp_max_it, mg_levels_richardson_scale, mg_levels_eigenvalues, mg_levels_esteig;
     KSP() sets them on a -pc_type mg KSP once one of them was touched or parsed. Likewise
     -ksp_norm_type (`.norm_type`, KSP_NORM_*; the C interface keeps it on the KSP object): KSP()
-    sets it unless it is KSP_NORM_DEFAULT."""
+    sets it unless it is KSP_NORM_DEFAULT. Likewise the settings of -ksp_type fgmres
+    (pb_ksp_fgmres_opts; `.fgmres`, with fgmres_restart / _haptol / _cgs_refinement): KSP() sets
+    them on a KSP of that type."""
 
     norm_type = property(lambda s: s.__dict__.get("norm_type", KSP_NORM_DEFAULT),
                          lambda s, v: s.__dict__.__setitem__("norm_type", int(v)))
@@ -428,6 +434,21 @@ class KspOptions(L.KspOpts):
     def mg_levels_esteig(self, v):
         self._mg().levels_esteig = (C.c_double * 4)(*v)
 
+    def _fgmres(self):
+        if "fgmres" not in self.__dict__:
+            f = L.KspFgmresOpts()
+            L.call("pb_ksp_fgmres_opts_default", C.byref(f))
+            self.__dict__["fgmres"] = f
+        return self.__dict__["fgmres"]
+
+    fgmres = property(_fgmres)
+    fgmres_restart = property(lambda s: s._fgmres().restart,
+                              lambda s, v: setattr(s._fgmres(), "restart", v))
+    fgmres_haptol = property(lambda s: s._fgmres().haptol,
+                             lambda s, v: setattr(s._fgmres(), "haptol", v))
+    fgmres_cgs_refinement = property(lambda s: s._fgmres().cgs_refinement,
+                                     lambda s, v: setattr(s._fgmres(), "cgs_refinement", v))
+
     def _cheb(self):
         if "chebyshev" not in self.__dict__:
             c = L.KspChebyshevOpts()
@@ -457,6 +478,7 @@ def ksp_options(argv=(), **kw):
         arr = (C.c_char_p * len(argv))(*[str(a).encode() for a in argv])
         L.call("pb_ksp_opts_parse", C.byref(o), len(argv), arr)
         L.call("pb_ksp_chebyshev_opts_parse", C.byref(o.chebyshev), len(argv), arr)
+        L.call("pb_ksp_fgmres_opts_parse", C.byref(o.fgmres), len(argv), arr)
         if any(str(a).startswith("-mg_") for a in argv):
             L.call("pb_pc_mg_opts_parse", C.byref(o.mg), len(argv), arr)
         nt = C.c_int(KSP_NORM_DEFAULT)
@@ -507,6 +529,12 @@ class KSP:
             except L.PbError:
                 self.destroy()
                 raise
+        if self.opts.ksp_type == KSP_FGMRES and isinstance(self.opts, KspOptions):
+            try:
+                L.call("pb_ksp_fgmres_set_opts", h, C.byref(self.opts.fgmres))
+            except L.PbError:
+                self.destroy()
+                raise
         # a KSP whose options never named the level smoother is given none (the default path)
         if self.opts.pc_type == PC_MG and "mg" in getattr(self.opts, "__dict__", {}):
             try:
@@ -529,7 +557,8 @@ class KSP:
     @property
     def norm_type(self):
         """(as set, in force): KSP_NORM_DEFAULT as set until set_norm_type; in force the default
-        is preconditioned (cg, richardson, chebyshev) or none (preonly)."""
+        is preconditioned (cg, richardson, chebyshev), unpreconditioned (fgmres) or none
+        (preonly)."""
         s, e = C.c_int(), C.c_int()
         L.call("pb_ksp_get_norm_type", self.h, C.byref(s), C.byref(e))
         return s.value, e.value
@@ -542,6 +571,20 @@ class KSP:
         m = L.PcMgOpts()
         L.call("pb_ksp_pc_mg_get_opts", self.h, C.byref(m))
         return m
+
+    def fgmres_set_opts(self, restart=None, haptol=None, cgs_refinement=None):
+        """pb_ksp_fgmres_set_opts: the fields given replace the KSP's current ones."""
+        f = self.fgmres_get_opts()
+        for name, v in (("restart", restart), ("haptol", haptol),
+                        ("cgs_refinement", cgs_refinement)):
+            if v is not None:
+                setattr(f, name, v)
+        L.call("pb_ksp_fgmres_set_opts", self.h, C.byref(f))
+
+    def fgmres_get_opts(self):
+        f = L.KspFgmresOpts()
+        L.call("pb_ksp_fgmres_get_opts", self.h, C.byref(f))
+        return f
 
     def solve(self, b, x):
         """Returns (reason, its, history): the res.nhist logged norms (its + 1 of them, its

@@ -159,6 +159,14 @@ __device__ __forceinline__ double cheb_step(double y, double ym1, double q, doub
   t = omega * t;
   return t + ym1;
 }
+// FGMRES on Jacobi / no PC (pb_ksp_fgmres.hip, FgLoad in pb_stencil.hip): the preconditioned
+// direction z = dinv (s wt) + shift from the unnormalised wt, v = s wt being the basis vector
+template <bool SHIFT>
+__device__ __forceinline__ double fg_z(double v, double dinv, double shift) {
+  double z = dinv * v;
+  if constexpr (SHIFT) z = z + shift;
+  return z;
+}
 // the level smoothers' zero-start cases: from y = ym1 = 0 with q = b, omega (scale (dinv b)),
 // and with ym1 = 0 (or Richardson: omega = 1), omega (y + scale (dinv q))
 __device__ __forceinline__ double poly_start_step(double b, double dinv, double scale,

@@ -76,11 +76,12 @@ __device__ __forceinline__ void maxpy_coefs(const MCoef& c, double* a) {
 
 // y = ((y + a0 x0) + a1 x1) + ...   (each product and each sum rounded: no FMA contraction; the
 // same order in the vector body and in the tail). from_zero: y is not read, the chain starts at
-// 0. y2: a second copy of the result. parts: per-block sums of y_new^2. NV = 0: only those sums
-// of y as it is (nothing stored).
+// 0. y2: a second copy of the result. parts: per-block sums of y_new^2 (wsum: two wide, with the
+// plain sum of y_new behind it). NV = 0: only those sums of y as it is (nothing stored).
 template <int NV>
 __global__ __launch_bounds__(256) void maxpy_kernel(double* y, double* y2, VecTable x, MCoef c,
-                                                    int64_t n, int from_zero, double* parts) {
+                                                    int64_t n, int from_zero, double* parts,
+                                                    int wsum) {
   constexpr int NA = NV > 0 ? NV : 1;
   double a[NA];
   maxpy_coefs<NV>(c, a);
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void maxpy_kernel(double* y, double* y2, VecTa
   dv2* yo2 = reinterpret_cast<dv2*>(y2);
   const int64_t n2 = n >> 1;
   const int64_t stride = (int64_t)gridDim.x * 256;
-  dv2 nrm = dv2{0.0, 0.0};
+  dv2 nrm = dv2{0.0, 0.0}, sm = dv2{0.0, 0.0};
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   for (; i + stride < n2; i += 2 * stride) {
     dv2 ya = dv2{0.0, 0.0}, yb = dv2{0.0, 0.0};
@@ -117,6 +118,8 @@ __global__ __launch_bounds__(256) void maxpy_kernel(double* y, double* y2, VecTa
     }
     nrm += ya * ya;
     nrm += yb * yb;
+    sm += ya;
+    sm += yb;
   }
   if (i < n2) {
     dv2 ya = dv2{0.0, 0.0};
@@ -131,8 +134,9 @@ __global__ __launch_bounds__(256) void maxpy_kernel(double* y, double* y2, VecTa
       if (y2) yo2[i] = ya;
     }
     nrm += ya * ya;
+    sm += ya;
   }
-  double s[1] = {nrm.x + nrm.y};
+  double s[2] = {nrm.x + nrm.y, sm.x + sm.y};
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // odd length: the last element
     double yt = from_zero ? 0.0 : y[n - 1];
 #pragma unroll
@@ -142,8 +146,11 @@ __global__ __launch_bounds__(256) void maxpy_kernel(double* y, double* y2, VecTa
       if (y2) y2[n - 1] = yt;
     }
     s[0] += yt * yt;
+    s[1] += yt;
   }
-  if (parts) block_partials<1>(s, parts);  // (uniform over the grid)
+  // (uniform over the grid)
+  if (parts && wsum) block_partials<2>(s, parts);
+  else if (parts) block_partials<1>(s, parts);
 }
 
 // out = a - b
@@ -200,7 +207,7 @@ int launch_mdot(pb_ctx* ctx, const double* x, int nv, const VecTable& y, int64_t
 }
 
 int launch_maxpy(pb_ctx* ctx, double* y, double* y2, int nv, const VecTable& x, const MCoef& c,
-                 int64_t n, bool from_zero, double* d_norm2) {
+                 int64_t n, bool from_zero, double* d_norm2, bool with_sum) {
   if (nv < 0 || nv > kMaxVecs) return set_error(PB_ERR_ARG, "multi-axpy of %d vectors", nv);
   const int nb = guess_grid(ctx, n >> 1);
   double* parts = d_norm2 ? ctx->d_partials : nullptr;
@@ -210,7 +217,7 @@ int launch_maxpy(pb_ctx* ctx, double* y, double* y2, int nv, const VecTable& x, 
 #define X(NV)                                                                                  \
   case NV:                                                                                     \
     hipLaunchKernelGGL(maxpy_kernel<NV>, dim3(nb), dim3(256), 0, ctx->stream, y, y2, x, c, n,  \
-                       from_zero ? 1 : 0, parts);                                              \
+                       from_zero ? 1 : 0, parts, with_sum ? 1 : 0);                            \
     break;
       X(0) PB_NV_CASES(X)
 #undef X
@@ -218,8 +225,9 @@ int launch_maxpy(pb_ctx* ctx, double* y, double* y2, int nv, const VecTable& x, 
     PB_HIP(hipGetLastError());
   }
   if (!d_norm2) return PB_OK;
-  PB_TRY(reduce_partials(ctx, ctx->d_partials, nb, 1, d_norm2));
-  return allreduce_device(ctx, d_norm2, 1);
+  const int width = with_sum ? 2 : 1;
+  PB_TRY(reduce_partials(ctx, ctx->d_partials, nb, width, d_norm2));
+  return allreduce_device(ctx, d_norm2, width);
 }
 
 int launch_guess_diff(pb_ctx* ctx, const double* a, const double* b, double* out, int64_t n) {

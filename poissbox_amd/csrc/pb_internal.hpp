@@ -611,9 +611,10 @@ struct MCoef {
 int launch_mdot(pb_ctx* ctx, const double* x, int nv, const VecTable& y, int64_t n, double* d_out);
 // y = ((y + a0 x0) + a1 x1) + ... (nv in 0..16; from_zero: y is written without being read, the
 // chain starts at 0); y2 != nullptr: the result is stored there too; d_norm2 != nullptr: the
-// global sum of y_new^2 is left there (nv = 0: of y as it is, nothing stored)
+// global sum of y_new^2 is left there (nv = 0: of y as it is, nothing stored); with_sum: and the
+// plain sum of y_new in d_norm2[1]
 int launch_maxpy(pb_ctx* ctx, double* y, double* y2, int nv, const VecTable& x, const MCoef& c,
-                 int64_t n, bool from_zero, double* d_norm2);
+                 int64_t n, bool from_zero, double* d_norm2, bool with_sum = false);
 int launch_guess_diff(pb_ctx* ctx, const double* a, const double* b, double* out, int64_t n);
 // b = s b, xdst = s xsrc in one launch
 int launch_guess_scale(pb_ctx* ctx, double* b, const double* xsrc, double* xdst, double s,

@@ -1,11 +1,15 @@
 // pb_ksp.hpp -- struct pb_ksp and what the KSP's host files share: pb_solver.cpp (create / begin /
 // iterate / end, the CG enqueue paths), pb_ksp_stationary.cpp (richardson, chebyshev, preonly),
 // pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers),
-// pb_norm_type.cpp (-ksp_norm_type) and pb_op.cpp (the operator).
+// pb_norm_type.cpp (-ksp_norm_type), pb_ksp_fgmres.cpp (fgmres) and pb_op.cpp (the operator).
 #pragma once
 #include <vector>
 
 #include "pb_internal.hpp"
+
+namespace pb {
+struct FgState;
+}
 
 struct pb_ksp {
   pb_op* A = nullptr;
@@ -15,6 +19,7 @@ struct pb_ksp {
   int norm_type = PB_KSP_NORM_DEFAULT;
   int norm() const {
     if (norm_type != PB_KSP_NORM_DEFAULT) return norm_type;
+    if (opts.ksp_type == PB_KSP_FGMRES) return PB_KSP_NORM_UNPRECONDITIONED;
     return opts.ksp_type == PB_KSP_PREONLY ? PB_KSP_NORM_NONE : PB_KSP_NORM_PRECONDITIONED;
   }
   // none (KSPConvergedSkip): nothing but a breakdown ends the solve before max_it, so the host
@@ -68,6 +73,21 @@ struct pb_ksp {
     double deltas[6] = {0, 0, 0, 0, 0, 0};
   };
   Cheb ch;
+  // Restarted flexible GMRES (-ksp_type fgmres). v[j] the orthonormal basis,
+  // z[j] = N(M^-1 v[j]) the stored preconditioned directions, both allocated in chunks as a cycle
+  // first reaches them (and cleared then). The unnormalised direction w alternates between pb[0]
+  // and pb[1] (wbuf(cur): the engine pass that forms v, z and A z from it writes the other), A x
+  // of a restart is r. pos = the host's cycle position: the device's (FgState::loc) as long as
+  // the state is not done. d: the Hessenberg, rotations and sums (device)
+  struct Fgmres {
+    pb_ksp_fgmres_opts opts;  // pb_ksp_fgmres_set_opts; the defaults from pb_ksp_create
+    std::vector<double*> v, z;
+    pb::FgState* d = nullptr;
+    int pos = 0;
+    int cur = 0;
+  };
+  Fgmres fgm;
+  bool fgmres() const { return opts.ksp_type == PB_KSP_FGMRES; }
   pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
   pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
@@ -155,6 +175,77 @@ int rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x);
 int enqueue_rich_iteration(pb_ksp* k);
 int rich_copy_back(pb_ksp* k, int64_t its);
 int solve_preonly(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res);
+
+// ---- pb_ksp_fgmres.cpp: -ksp_type fgmres ----
+// pb_ksp_begin's setup (as rich_begin), one Arnoldi step of pb_ksp_iterate (with the restart
+// sequence after the cycle's last), pb_ksp_end's solution build from the cycle the solve ended
+// in, and pb_ksp_destroy's share
+int fgmres_create(pb_ksp* k);
+int fgmres_begin(pb_ksp* k, const pb_vec* b, pb_vec* x);
+int enqueue_fgmres_iteration(pb_ksp* k);
+int fgmres_finish(pb_ksp* k);
+void fgmres_destroy(pb_ksp* k);
+int check_fgmres_opts(const pb_ksp_fgmres_opts* o);
+
+// ---- pb_ksp_fgmres.hip: the small state and its kernels ----
+constexpr int kFgMaxRestart = 64;
+constexpr int kFgLd = kFgMaxRestart + 1;  // column stride of the Hessenberg
+// Everything small of a cycle, device resident. Column k of the Hessenberg (rotated in place into
+// the triangular factor) is hh[k * kFgLd .. + k + 1]. The tolerances, reason, done flag and
+// history cursor are CgState's (pb_ksp::d_st)
+struct FgState {
+  double hh[kFgLd * kFgMaxRestart];
+  double cs[kFgMaxRestart], sn[kFgMaxRestart];  // Givens cosines and sines
+  double g[kFgLd];                              // the rotated right-hand side
+  double y[kFgMaxRestart];                      // the triangular solve's result
+  double dots[kFgLd], dots2[kFgLd];             // the multi-dot's sums (second: refinement pass)
+  double nrm2;    // sum w^2 from the multi-axpy (a restart, the setup: sum r^2)
+  double wsum;    // sum w beside it (nrm2, wsum: the multi-axpy's two sums, adjacent)
+  double shift;   // Jacobi / no PC: the null-space shift of the next z, -(dinv (scale wsum)) / ntot
+  double bsq;     // sum b^2 (the reference norm of a nonzero guess)
+  double zsum;    // sum of M^-1 v_k: the null-space shift is -zsum / ntot
+  double scale;   // 1 / h_(k+1,k) (a cycle's start: 1 / ||r||)
+  double haptol;
+  int loc;        // cycle position: steps done in this cycle = live entries of v, z, y
+  int restart;
+};
+// at most kFgMaxRestart vectors by value in the kernel arguments
+struct FgTable {
+  const double* p[kFgMaxRestart];
+};
+// v = fs->scale w; exits at entry when the state is done (so do the two below)
+int launch_fg_scale(pb_ctx* ctx, const double* w, double* v, const FgState* fs, const CgState* st,
+                    int64_t n);
+// the sum of z as a stored-z PC wrote it, reduced and allreduced into fs->zsum
+int launch_fg_zsum(pb_ctx* ctx, const double* z, FgState* fs, const CgState* st, int64_t n);
+// z = z + (-(fs->zsum / ntot)): MatNullSpaceRemove's VecShift
+int launch_fg_shift(pb_ctx* ctx, double* z, const FgState* fs, const CgState* st, int64_t n);
+// Jacobi / no PC: z = dinv v + fs->shift (nullspace = 0: no add) -- fg_z, the expression the
+// engine pass forms on load
+int launch_fg_pcshift(pb_ctx* ctx, const double* v, double* z, const FgState* fs,
+                      const CgState* st, int64_t n, bool nullspace);
+// The engine pass of a step on the 7-point operator with Jacobi / no PC (one rank, wrap planes;
+// pb_stencil.hip FgLoad / FgEpi): from the unnormalised direction wt, v = fs->scale wt and
+// z = dinv v + fs->shift formed on load; stores v and z and writes w_out = A z (another buffer
+// than wt). 8 B read, 24 B written per DoF; the bits of scale + pcshift + operator
+int launch_fg_fused(pb_grid* g, const Star& s, const double* wt, double* v, double* z,
+                    double* w_out, const FgState* fs, const CgState* st, bool nullspace);
+// mode 0: the setup (||r_0|| from fs->nrm2, the reference from fs->bsq by ref = REF_*, history[0],
+// the first test, restart / haptol into the state); mode 1: a restart (the recomputed ||r||
+// tested at the same iteration count, not logged). Both start a cycle: loc = 0, g_0 = ||r||,
+// scale = 1 / ||r||
+int launch_fg_start(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_done, int mode,
+                    int ref, int restart, double haptol, int64_t host_iter);
+// one Arnoldi step's scalar part: the column from the sums (passes = 2: dots + dots2), the
+// happy-breakdown check, the rotations, the estimate logged and tested, the done flag
+int launch_fg_step(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_done, int passes,
+                   int64_t host_iter);
+// y = the triangular solve over the live columns; x = x + (((0 + y_0 z_0) + y_1 z_1) + ...) over
+// the live count read from the device. force = false: exit at entry when the state is done (a
+// restart enqueued ahead); true: pb_ksp_end's build of the cycle the solve ended in
+int launch_fg_trisolve(pb_ctx* ctx, const CgState* st, FgState* fs, bool force);
+int launch_fg_build(pb_ctx* ctx, double* x, const FgTable& z, const FgState* fs, const CgState* st,
+                    bool force, int64_t n);
 
 // ---- pb_ksp_guess.cpp: -ksp_guess_type fischer ----
 int solve_projected(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,

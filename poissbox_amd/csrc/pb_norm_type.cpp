@@ -50,6 +50,9 @@ int pb_ksp_set_norm_type(pb_ksp* k, int type) {
   if (k->rich() && type == PB_KSP_NORM_NATURAL)
     return set_error(PB_ERR_UNSUPPORTED, "-ksp_type %s does not support the natural norm",
                      k->cheb() ? "chebyshev" : "richardson");
+  if (k->fgmres() && (type == PB_KSP_NORM_PRECONDITIONED || type == PB_KSP_NORM_NATURAL))
+    return set_error(PB_ERR_UNSUPPORTED, "-ksp_type fgmres is right-preconditioned: "
+                                         "-ksp_norm_type unpreconditioned or none");
   k->norm_type = type;
   return PB_OK;
 }

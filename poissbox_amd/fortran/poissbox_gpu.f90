@@ -71,6 +71,12 @@ module poissbox_gpu
      real(c_double) :: esteig(4)             ! -ksp_chebyshev_esteig a,b,c,d (0, 0.1, 0, 1.1)
      integer(c_int) :: esteig_steps          ! -ksp_chebyshev_esteig_steps (10)
   end type pb_ksp_chebyshev_opts
+  !! -ksp_type fgmres's settings (a struct of their own: pb_ksp_fgmres_set_opts)
+  type, bind(C), public :: pb_ksp_fgmres_opts
+     integer(c_int) :: restart               ! -ksp_gmres_restart (30), 1..64
+     real(c_double) :: haptol                ! -ksp_gmres_haptol (1e-30)
+     integer(c_int) :: cgs_refinement        ! refine_never (0) | refine_always (2)
+  end type pb_ksp_fgmres_opts
 
   !! -pc_type mg's level smoother (-mg_levels_*; a struct of its own: pb_ksp_pc_mg_set_opts)
   type, bind(C), public :: pb_pc_mg_opts
@@ -116,6 +122,9 @@ module poissbox_gpu
   public :: c_pb_ksp_chebyshev_get_eigenvalues, c_pb_tridiag_extreme_eigenvalues
   public :: c_pb_ksp_chebyshev_opts_default, c_pb_ksp_chebyshev_opts_parse
   public :: c_pb_ksp_chebyshev_set_opts, c_pb_solve_chebyshev
+  ! -ksp_type fgmres: restarted flexible GMRES (-ksp_gmres_restart, _haptol, _cgs_refinement_type)
+  public :: c_pb_ksp_fgmres_opts_default, c_pb_ksp_fgmres_opts_parse
+  public :: c_pb_ksp_fgmres_set_opts, c_pb_ksp_fgmres_get_opts, c_pb_solve_fgmres
   ! -pc_type mg: the level smoother (-mg_levels_ksp_type, -mg_levels_pc_type, ...)
   public :: c_pb_pc_mg_opts_default, c_pb_pc_mg_opts_parse, c_pb_ksp_pc_mg_set_opts
   public :: c_pb_ksp_pc_mg_get_opts, c_pb_solve_mg
@@ -468,6 +477,39 @@ module poissbox_gpu
        type(c_ptr), value :: ksp
        type(pb_ksp_chebyshev_opts) :: o
      end function
+     integer(c_int) function c_pb_ksp_fgmres_opts_default(o) &
+          bind(C, name="pb_ksp_fgmres_opts_default")
+       import :: c_int, pb_ksp_fgmres_opts
+       type(pb_ksp_fgmres_opts) :: o
+     end function
+     integer(c_int) function c_pb_ksp_fgmres_opts_parse(o, argc, argv) &
+          bind(C, name="pb_ksp_fgmres_opts_parse")
+       import :: c_int, c_ptr, pb_ksp_fgmres_opts
+       type(pb_ksp_fgmres_opts) :: o
+       integer(c_int), value :: argc
+       type(c_ptr) :: argv(*)
+     end function
+     integer(c_int) function c_pb_ksp_fgmres_set_opts(ksp, o) &
+          bind(C, name="pb_ksp_fgmres_set_opts")
+       import :: c_int, c_ptr, pb_ksp_fgmres_opts
+       type(c_ptr), value :: ksp
+       type(pb_ksp_fgmres_opts) :: o
+     end function
+     integer(c_int) function c_pb_ksp_fgmres_get_opts(ksp, o) &
+          bind(C, name="pb_ksp_fgmres_get_opts")
+       import :: c_int, c_ptr, pb_ksp_fgmres_opts
+       type(c_ptr), value :: ksp
+       type(pb_ksp_fgmres_opts) :: o
+     end function
+     integer(c_int) function c_pb_solve_fgmres(A, P, o, fo, b, x, res, hist, cap) &
+          bind(C, name="pb_solve_fgmres")
+       import :: c_int, c_ptr, c_int64_t, pb_ksp_opts, pb_ksp_fgmres_opts, pb_ksp_result
+       type(c_ptr), value :: A, P, b, x, hist
+       type(pb_ksp_opts) :: o
+       type(pb_ksp_fgmres_opts) :: fo
+       type(pb_ksp_result) :: res
+       integer(c_int64_t), value :: cap
+     end function
      integer(c_int) function c_pb_solve_chebyshev(A, P, o, co, b, x, res, hist, cap) &
           bind(C, name="pb_solve_chebyshev")
        import :: c_int, c_ptr, c_int64_t, pb_ksp_opts, pb_ksp_chebyshev_opts, pb_ksp_result
@@ -797,6 +839,7 @@ contains
     real(pb_dp), intent(out), optional :: rnorm
     type(pb_ksp_opts) :: o
     type(pb_ksp_chebyshev_opts) :: co
+    type(pb_ksp_fgmres_opts) :: fo
     type(pb_pc_mg_opts) :: mo
     type(pb_ksp_result) :: res
     integer :: nargs, i, l, lmax
@@ -822,6 +865,8 @@ contains
     ierr = c_pb_ksp_opts_parse(o, int(nargs, c_int), argv)
     if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_default(co)
     if (ierr == 0) ierr = c_pb_ksp_chebyshev_opts_parse(co, int(nargs, c_int), argv)
+    if (ierr == 0) ierr = c_pb_ksp_fgmres_opts_default(fo)
+    if (ierr == 0) ierr = c_pb_ksp_fgmres_opts_parse(fo, int(nargs, c_int), argv)
     if (ierr == 0) ierr = c_pb_pc_mg_opts_default(mo)
     if (ierr == 0) ierr = c_pb_pc_mg_opts_parse(mo, int(nargs, c_int), argv)
     norm_type = PB_KSP_NORM_DEFAULT
@@ -834,7 +879,8 @@ contains
     ! (the Chebyshev settings are read by a KSP of that type only)
     ! (-pc_type mg under another KSP type takes its level smoother, -mg_levels_*, instead)
     ! (-ksp_norm_type lives on the KSP object, as KSPSetNormType: a KSP for this one solve)
-    if (norm_type /= PB_KSP_NORM_DEFAULT) then
+    ! (-ksp_type fgmres: its settings and, under it, the multigrid's level smoother: a KSP too)
+    if (norm_type /= PB_KSP_NORM_DEFAULT .or. o%ksp_type == 4) then
        ksp = c_null_ptr
        ierr = c_pb_ksp_create(A%h, P%h, o, ksp)
        if (ierr == 0) then
@@ -843,7 +889,9 @@ contains
           else if (o%pc_type == 3) then
              ierr = c_pb_ksp_pc_mg_set_opts(ksp, mo)
           end if
-          if (ierr == 0) ierr = c_pb_ksp_set_norm_type(ksp, norm_type)
+          if (ierr == 0 .and. o%ksp_type == 4) ierr = c_pb_ksp_fgmres_set_opts(ksp, fo)
+          if (ierr == 0 .and. norm_type /= PB_KSP_NORM_DEFAULT) &
+               ierr = c_pb_ksp_set_norm_type(ksp, norm_type)
           if (ierr == 0) ierr = c_pb_ksp_solve(ksp, b%h, x%h, res, c_null_ptr, 0_c_int64_t)
           ierr2 = c_pb_ksp_destroy(ksp)  ! (a successful destroy leaves the last error's text)
           if (ierr == 0) ierr = ierr2
