@@ -269,10 +269,31 @@ int pb_vec_get_ownership_range(const pb_vec* v, int64_t* first, int64_t* next);
  *    7-point operator with Jacobi / no PC (one rank) a step starts with one engine pass that forms
  *    and stores v_k and z_k and writes A z_k; there the mean of z_k is taken from the sum of the
  *    unnormalised direction (equal in exact arithmetic to the mean over z_k).
+ *  PB_KSP_PIPECG (PETSc KSPSolve_PIPECG, Ghysels & Vanroose: pipelined CG, PC_LEFT, default test):
+ *    CG in exact arithmetic with ONE reduction per iteration, on every operator and with every
+ *    PC (the PC is applied to a stored vector like any other) -- what cg_single_reduction gives
+ *    the 7-point operator with Jacobi / no PC only. r = b - A x, u = N(M^-1 r), w = A u; iteration
+ *    i: gamma = r.u, delta = w.u and the norm's sum in one reduction; m = N(M^-1 w), n = A m;
+ *    the norm is logged and tested with its = i; beta = gamma / gamma_old (0 at i = 0),
+ *    alpha = gamma / (delta - (beta / alpha_old) gamma) (gamma / delta at i = 0); z = n + beta z,
+ *    q = m + beta q, s = w + beta s, p = u + beta p; x += alpha p, r -= alpha s, u -= alpha q,
+ *    w -= alpha z. nhist = its + 1 always; entry k is the norm after k updates. After max_it
+ *    updates one more norm is logged and tested before PB_KSP_DIVERGED_ITS (PETSc's loop makes
+ *    one more update first: a deviation). All four norm types (preconditioned
+ *    ||u||, the default; unpreconditioned ||r||; natural sqrt|gamma|; none) come out of the one
+ *    reduction; the reference norm with a nonzero guess follows PB_KSP_CG's rules. There is no
+ *    indefinite-PC or indefinite-matrix test (PETSc's pipecg has none): a zero or non-finite
+ *    denominator surfaces as PB_KSP_DIVERGED_NANORINF at the next test. b and x must be
+ *    distinct. guess_type fischer is PB_ERR_UNSUPPORTED with it. It moves 128 B/DoF per
+ *    iteration where CG moves 56: on one GPU CG is faster; the type is there for what it does
+ *    between ranks and for callers who want the method. With sor / mg / fft the mean of M^-1 w
+ *    is a second, one-double allreduce. The KSP keeps 8 fields (9 off the engine path;
+ *    INTEGRATION.md). Parity unpinned: written from knowledge of pipecg.c, pinned to a numpy
+ *    restatement (tests/pipecg_restatement.py).
  * cg_single_reduction is a CG option: the other types ignore it. */
 enum pb_ksp_type {
   PB_KSP_CG = 0, PB_KSP_PREONLY = 1, PB_KSP_RICHARDSON = 2, PB_KSP_CHEBYSHEV = 3,
-  PB_KSP_FGMRES = 4
+  PB_KSP_FGMRES = 4, PB_KSP_PIPECG = 5
 };
 /* seed of the noise vector (pb_vec_set_random) the Chebyshev eigenvalue estimate starts from */
 #define PB_CHEBYSHEV_ESTEIG_SEED 20240607ULL
@@ -298,7 +319,7 @@ typedef struct {
   double atol;       /* -ksp_atol   (1e-50)               */
   double dtol;       /* -ksp_divtol (1e5)                 */
   int64_t max_it;    /* -ksp_max_it (10000)               */
-  int ksp_type;      /* -ksp_type cg|preonly|richardson|chebyshev|fgmres */
+  int ksp_type;      /* -ksp_type cg|preonly|richardson|chebyshev|fgmres|pipecg */
   int pc_type;       /* -pc_type none|jacobi|sor|mg       */
   int nullspace;     /* constant null space (src/poissbox.f90:285-291), default 1 */
   int monitor;       /* -ksp_monitor: print ||z_k|| per iteration after the solve (rank 0) */
@@ -406,7 +427,7 @@ typedef struct {
                         after a breakdown exit (beta = 0, indefinite PC / matrix) */
 } pb_ksp_result;
 int pb_ksp_opts_default(pb_ksp_opts* opts);
-/* Parses PETSc-style options (-ksp_type cg|preonly|richardson|chebyshev|fgmres,
+/* Parses PETSc-style options (-ksp_type cg|preonly|richardson|chebyshev|fgmres|pipecg,
  * -ksp_richardson_scale,
  * -pc_type,
  * -ksp_rtol, -ksp_atol, -ksp_divtol, -ksp_max_it, -ksp_monitor, -ksp_converged_reason, -pc_mg_levels, -pc_mg_coarse_its,
@@ -443,11 +464,11 @@ int pb_ksp_destroy(pb_ksp* ksp);
 /* ≙ KSPSetNormType / -ksp_norm_type: the number the solve logs, tests and returns (history,
  * pb_ksp_result.rnorm, rnorm0). z = N(M^-1 r) and the iteration (alpha, beta, p, x, r) are the same
  * under every type; the values are PETSc's KSPNormType.
- *   preconditioned (the default of cg / richardson / chebyshev): ||z_i||_2; from a nonzero guess the
+ *   preconditioned (the default of cg / richardson / chebyshev / pipecg): ||z_i||_2; from a nonzero guess the
  *     reference is ||N(M^-1 b)||. PB_KSP_FGMRES is right-preconditioned: its default is
  *     unpreconditioned, and preconditioned / natural are PB_ERR_UNSUPPORTED on it
  *   unpreconditioned: ||r_i||_2 = ||b - A x_i||_2, the plain 2-norm (no mean shift); reference ||b||_2
- *   natural (cg only): sqrt(|r_i . z_i|); reference sqrt(|b . N(M^-1 b)|)
+ *   natural (cg and pipecg only): sqrt(|r_i . z_i|); reference sqrt(|b . N(M^-1 b)|)
  *   none: no norm and no test (KSPConvergedSkip): the solve runs max_it iterations and ends with
  *     PB_KSP_CONVERGED_ITS, its = max_it, rnorm = rnorm0 = 0 and its + 1 history entries of 0.0;
  *     breakdown and NaN exits of the dots stay. pb_ksp_solve enqueues every iteration and waits once.
@@ -471,8 +492,8 @@ int pb_ksp_norm_type_parse(int* type, int argc, const char* const* argv);
  * PB_ERR_STATE between pb_ksp_begin and pb_ksp_end. An error leaves the KSP as it was. */
 int pb_ksp_set_norm_type(pb_ksp* ksp, int type);
 /* ≙ KSPGetNormType. *set: the value as set (PB_KSP_NORM_DEFAULT after create); *effective: the one
- * in force (default: preconditioned for cg / richardson / chebyshev, unpreconditioned for fgmres,
- * none for preonly). Either may be NULL. */
+ * in force (default: preconditioned for cg / richardson / chebyshev / pipecg, unpreconditioned for
+ * fgmres, none for preonly). Either may be NULL. */
 int pb_ksp_get_norm_type(const pb_ksp* ksp, int* set, int* effective);
 /* -ksp_chebyshev_eigenvalues emin,emax, -ksp_chebyshev_esteig a,b,c,d,
  * -ksp_chebyshev_esteig_steps n, -ksp_chebyshev_esteig_noisy [bool] from the same argument list

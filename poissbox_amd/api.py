@@ -28,7 +28,9 @@ PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
 # (-ksp_chebyshev_eigenvalues emin,emax; estimated when not given: KSP.chebyshev_eigenvalues())
 # fgmres = restarted flexible GMRES (right-preconditioned: the tested number is ||b - A x||;
 # -ksp_gmres_restart, -ksp_gmres_haptol, -ksp_gmres_cgs_refinement_type: pb_ksp_fgmres_opts)
-KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV, KSP_FGMRES = 0, 1, 2, 3, 4
+# pipecg = pipelined CG (KSPPIPECG): CG in exact arithmetic with one reduction per iteration on
+# every operator and PC; no options of its own
+KSP_CG, KSP_PREONLY, KSP_RICHARDSON, KSP_CHEBYSHEV, KSP_FGMRES, KSP_PIPECG = 0, 1, 2, 3, 4, 5
 FGMRES_REFINE_NEVER, FGMRES_REFINE_ALWAYS = 0, 2
 # -mg_levels_ksp_type / -mg_levels_pc_type: the level smoother of -pc_type mg (pb_pc_mg_opts)
 MG_LEVELS_RICHARDSON, MG_LEVELS_CHEBYSHEV = 0, 1
@@ -557,7 +559,7 @@ class KSP:
     @property
     def norm_type(self):
         """(as set, in force): KSP_NORM_DEFAULT as set until set_norm_type; in force the default
-        is preconditioned (cg, richardson, chebyshev), unpreconditioned (fgmres) or none
+        is preconditioned (cg, richardson, chebyshev, pipecg), unpreconditioned (fgmres) or none
         (preonly)."""
         s, e = C.c_int(), C.c_int()
         L.call("pb_ksp_get_norm_type", self.h, C.byref(s), C.byref(e))

@@ -75,6 +75,22 @@ __device__ __forceinline__ double cg_dp(const CgState& st, const double* S, doub
 // how KSPConvergedDefault picks its reference norm when the solve starts from a nonzero guess
 enum { REF_RHS = 0, REF_INITIAL = 1, REF_MIN = 2, REF_ZERO_GUESS = 3 };
 
+// KSPConvergedDefault on the norm dp with its = st.its (rtol / atol / dtol; a NaN or Inf is
+// DIVERGED_NANORINF); KSPConvergedSkip (-ksp_norm_type none) tests the count alone. dtol_test is
+// false at the setup of a zero guess, where dp is the reference itself (fgmres, pipecg)
+__device__ __forceinline__ void ksp_default_test(CgState& st, double dp, bool dtol_test) {
+  const bool skip = st.norm == PB_KSP_NORM_NONE;
+  if (!finite(dp)) {
+    st.reason = PB_KSP_DIVERGED_NANORINF;
+  } else if (skip) {
+    if (st.its >= st.max_it) st.reason = PB_KSP_CONVERGED_ITS;
+  } else if (dp <= st.ttol) {
+    st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
+  } else if (dtol_test && dp >= st.dtol * st.rnorm0) {
+    st.reason = PB_KSP_DIVERGED_DTOL;
+  }
+}
+
 // stage 0 (after init / the first PC apply): S = (sum t, sum t^2, sum t.r, sum r).
 // ref = REF_ZERO_GUESS: x0 = 0, the reference norm is ||z_0|| itself. Nonzero guess
 // (KSPConvergedDefault, PETSc): bnorm = ||N(M^-1 b)|| is the reference (REF_RHS; ||z_0|| when it

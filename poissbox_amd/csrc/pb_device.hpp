@@ -167,6 +167,35 @@ __device__ __forceinline__ double fg_z(double v, double dinv, double shift) {
   if constexpr (SHIFT) z = z + shift;
   return z;
 }
+// Pipelined CG (pb_ksp_pipecg.hip, PcgLoad / PcgEpi in pb_stencil.hip). The preconditioned
+// vector is m = fg_z(w, dinv, shift) with the null-space shift from the sum of what the PC is
+// applied to (Jacobi / no PC: sum w, which rides in the iteration's one reduction) or, with
+// dinv = 1, from the sum of a stored M^-1 w: -((dinv sum) / ntot)
+__device__ __forceinline__ double pcg_shift(double dinv, double sum, double ntot) {
+  return -((dinv * sum) / ntot);
+}
+// one point of the iteration's eight updates (first: KSPSolve_PIPECG's i = 0, where z, q, s, p
+// are set, not read: whatever they hold is discarded) and the five sums of the new values:
+// gamma = r.u, delta = w.u, sum u^2, sum r^2, sum w
+__device__ __forceinline__ void pcg_update(bool first, double alpha, double beta, double m,
+                                           double n, double& z, double& q, double& s, double& p,
+                                           double& x, double& r, double& u, double& w,
+                                           double* acc) {
+  const double zb = n + beta * z, qb = m + beta * q, sb = w + beta * s, pb = u + beta * p;
+  z = first ? n : zb;
+  q = first ? m : qb;
+  s = first ? w : sb;
+  p = first ? u : pb;
+  x = x + alpha * p;
+  r = r - alpha * s;
+  u = u - alpha * q;
+  w = w - alpha * z;
+  acc[0] += r * u;
+  acc[1] += w * u;
+  acc[2] += u * u;
+  acc[3] += r * r;
+  acc[4] += w;
+}
 // the level smoothers' zero-start cases: from y = ym1 = 0 with q = b, omega (scale (dinv b)),
 // and with ym1 = 0 (or Richardson: omega = 1), omega (y + scale (dinv q))
 __device__ __forceinline__ double poly_start_step(double b, double dinv, double scale,

@@ -1,7 +1,8 @@
 // pb_ksp.hpp -- struct pb_ksp and what the KSP's host files share: pb_solver.cpp (create / begin /
 // iterate / end, the CG enqueue paths), pb_ksp_stationary.cpp (richardson, chebyshev, preonly),
 // pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers),
-// pb_norm_type.cpp (-ksp_norm_type), pb_ksp_fgmres.cpp (fgmres) and pb_op.cpp (the operator).
+// pb_norm_type.cpp (-ksp_norm_type), pb_ksp_fgmres.cpp (fgmres), pb_ksp_pipecg.cpp (pipecg) and
+// pb_op.cpp (the operator).
 #pragma once
 #include <vector>
 
@@ -9,6 +10,7 @@
 
 namespace pb {
 struct FgState;
+struct PcgState;
 }
 
 struct pb_ksp {
@@ -88,6 +90,26 @@ struct pb_ksp {
   };
   Fgmres fgm;
   bool fgmres() const { return opts.ksp_type == PB_KSP_FGMRES; }
+  // Pipelined CG (-ksp_type pipecg). Beside x and b: r (r), u = N(M^-1 r)
+  // (pb[0]), w = A u and the four recurrence vectors z, q, s, p. On the 7-point operator with
+  // Jacobi / no PC (one rank) the engine pass of update i reads w from wbuf(i) and writes
+  // wbuf(i + 1) (pb[1], w2): neighbouring waves still read w around a point. cur = the host's
+  // parity, the device's as long as the state is not done (a launch that exited at entry wrote
+  // nothing, and nothing reads w after the solve). Elsewhere w stays in pb[1] and m = N(M^-1 w),
+  // n = A m are stored (the KSP's w and z fields). d: the sums and scalars (device)
+  struct Pipecg {
+    double* z = nullptr;
+    double* q = nullptr;
+    double* s = nullptr;
+    double* p = nullptr;
+    double* w2 = nullptr;
+    pb::PcgState* d = nullptr;
+    int cur = 0;
+    bool fused = false;  // this solve runs the engine pass (decided by pb_ksp_begin)
+  };
+  Pipecg pcg;
+  bool pipecg() const { return opts.ksp_type == PB_KSP_PIPECG; }
+  double* pcg_wbuf(int i) const { return (i & 1) ? pcg.w2 : pb[1]; }
   pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
   pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
@@ -246,6 +268,60 @@ int launch_fg_step(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_d
 int launch_fg_trisolve(pb_ctx* ctx, const CgState* st, FgState* fs, bool force);
 int launch_fg_build(pb_ctx* ctx, double* x, const FgTable& z, const FgState* fs, const CgState* st,
                     bool force, int64_t n);
+
+// ---- pb_ksp_pipecg.cpp: -ksp_type pipecg ----
+// pb_ksp_create's share, pb_ksp_begin's setup (as rich_begin), one iteration of pb_ksp_iterate
+// (x is updated in place: pb_ksp_end has nothing to add) and pb_ksp_destroy's share
+int pipecg_create(pb_ksp* k);
+int pipecg_begin(pb_ksp* k, const pb_vec* b, pb_vec* x);
+int enqueue_pipecg_iteration(pb_ksp* k);
+void pipecg_destroy(pb_ksp* k);
+
+// ---- pb_ksp_pipecg.hip: the small state and its kernels ----
+constexpr int kPcgSums = 5;
+// sums: gamma = r.u, delta = w.u, sum u^2, sum r^2, sum w of the current vectors -- one reduction
+// (split contexts: one allreduce). The tolerances, reason, done flag, update count (CgState::it)
+// and history cursor are CgState's (pb_ksp::d_st)
+struct PcgState {
+  double sums[kPcgSums];
+  double bsums[kPcgSums];  // the same sums with b for r and N(M^-1 b) for u and w (nonzero guess)
+  double gamma_old, alpha, beta;
+  double zsum;  // sum of M^-1 w as a stored-z PC wrote it (the setup with Jacobi / no PC: sum r)
+};
+// the vectors of an update; w_out = w (in place) but in the engine pass
+struct PcgVecs {
+  double *z, *q, *s, *p, *x, *r, *u;
+  const double* w;
+  double* w_out;
+};
+// *dst = the global sum of v (exits at entry when skip and the state is done, as the two below)
+int launch_pcg_sum(pb_ctx* ctx, const double* v, double* dst, const CgState* st, bool skip,
+                   int64_t n);
+// dst = dinv src + shift, shift = -((dinv *sum) / ntot) (nullspace = 0: no add): fg_z with
+// pcg_shift, the expression the engine pass forms on load. dst may be src
+int launch_pcg_pcshift(pb_ctx* ctx, const double* src, double* dst, const double* sum,
+                       const CgState* st, bool skip, int64_t n, bool nullspace);
+// the five sums of (r, u, w) as they are, reduced and allreduced into dst (the setup)
+int launch_pcg_sums(pb_ctx* ctx, const double* r, const double* u, const double* w, double* dst,
+                    int64_t n);
+// One block: reduces the nparts x 5 partials of the update pass into ps->sums (nparts = 0: the
+// sums are there already, allreduced), then the scalar step: the norm by -ksp_norm_type logged and
+// tested (KSPConvergedDefault), the iteration limit, beta, alpha (the i = 0 branch from the
+// device's update count), the done flag. setup: pb_ksp_begin's (ref = REF_*, its = 0), else the
+// update count advances first
+int launch_pcg_finalize(pb_ctx* ctx, CgState* st, PcgState* ps, const double* parts, int nparts,
+                        double* hist, int* h_done, bool setup, int ref, int64_t host_iter);
+// ---- pb_stencil.hip ----
+// The iteration on the 7-point operator with Jacobi / no PC (one rank, wrap planes; PcgLoad /
+// PcgEpi): m = dinv w + shift formed on load, n = A m, the eight updates and the five sums of the
+// new values; v.w_out is another buffer than v.w. 64 B read, 64 B written per DoF
+int launch_pcg_fused(pb_grid* g, const Star& s, const PcgVecs& v, const PcgState* ps,
+                     const CgState* st, bool nullspace, int* nparts);
+// The same updates and sums from stored m and n, in the engine's tiles, chunks and order of
+// summation (the bits of the engine pass): the stored-z PCs, the compact and assembled operators,
+// N ranks, tuning pipecg_fused = 0. 80 B read, 64 B written per DoF
+int launch_pcg_update(pb_grid* g, const double* m, const double* n, const PcgVecs& v,
+                      const PcgState* ps, const CgState* st, int* nparts);
 
 // ---- pb_ksp_guess.cpp: -ksp_guess_type fischer ----
 int solve_projected(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,

@@ -86,22 +86,6 @@ __global__ __launch_bounds__(256) void fg_shift_kernel(double* __restrict__ z,
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) z[n - 1] = z[n - 1] + shift;
 }
 
-// KSPConvergedDefault on the norm dp with its = st.its (rtol / atol / dtol; a NaN or Inf is
-// DIVERGED_NANORINF); KSPConvergedSkip (-ksp_norm_type none) tests the count alone. dtol_test is
-// false at the setup of a zero guess, where dp is the reference itself
-__device__ __forceinline__ void fg_test(CgState& st, double dp, bool dtol_test) {
-  const bool skip = st.norm == PB_KSP_NORM_NONE;
-  if (!finite(dp)) {
-    st.reason = PB_KSP_DIVERGED_NANORINF;
-  } else if (skip) {
-    if (st.its >= st.max_it) st.reason = PB_KSP_CONVERGED_ITS;
-  } else if (dp <= st.ttol) {
-    st.reason = dp < st.atol ? PB_KSP_CONVERGED_ATOL : PB_KSP_CONVERGED_RTOL;
-  } else if (dtol_test && dp >= st.dtol * st.rnorm0) {
-    st.reason = PB_KSP_DIVERGED_DTOL;
-  }
-}
-
 // Jacobi / no PC: the next direction is z = dinv (scale w) + shift, and its mean follows from the
 // sum of w the multi-axpy took: shift = -(dinv (scale sum w)) / ntot
 __device__ __forceinline__ void fg_next_shift(const CgState& st, FgState* fs) {
@@ -137,14 +121,14 @@ __global__ void fg_start_kernel(CgState* st_g, FgState* fs, double* hist, int* h
     if (st.nhist > 0 && hist) hist[0] = rn;
     st.nlog = st.nhist > 0 ? 1 : 0;
     st.ttol = fmax(st.rtol * rn0, st.atol);
-    fg_test(st, rn, ref != REF_ZERO_GUESS);
+    ksp_default_test(st, rn, ref != REF_ZERO_GUESS);
     // (KSPSolve_FGMRES leaves its loop without a step at max_it = 0)
     if (!st.reason && st.max_it <= 0) st.reason = PB_KSP_DIVERGED_ITS;
     st.done = st.reason != 0;
     if (h_done) h_done[0] = st.done;
   } else {
     // a restart: the recomputed ||b - A x|| at the iteration count the cycle ended with
-    fg_test(st, rn, true);
+    ksp_default_test(st, rn, true);
     st.done = st.reason != 0;
     if (h_done) h_done[host_iter + 1] = st.done;
   }
@@ -218,7 +202,7 @@ __global__ void fg_step_kernel(CgState* st_g, FgState* fs, double* hist, int* h_
       if (hist) hist[st.its] = res;
       st.nlog = st.its + 1;
     }
-    fg_test(st, res, true);
+    ksp_default_test(st, res, true);
     if (!st.reason && hapend)
       st.reason = st.norm == PB_KSP_NORM_NONE ? PB_KSP_CONVERGED_HAPPY_BREAKDOWN
                                               : PB_KSP_DIVERGED_BREAKDOWN;

@@ -2,7 +2,8 @@
 // and the KSP's setter and getter. The value lives on the KSP object, not in pb_ksp_opts (whose
 // layout and parser stay as they are: pb_ksp_opts_parse skips the option as unknown). What the
 // types mean on the device is in pb_cg_device.hpp (cg_dp, the CG stages) and
-// pb_ksp_stationary.hip (rich_stage); DESIGN.md §3.1g.
+// pb_ksp_stationary.hip (rich_stage); DESIGN.md §3.1g. -ksp_type pipecg takes all four (its default
+// is preconditioned): every one comes out of its one reduction (pcg_dp, pb_ksp_pipecg.hip).
 #include <cstring>
 
 #include "pb_ksp.hpp"

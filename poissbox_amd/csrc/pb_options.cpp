@@ -227,7 +227,8 @@ struct EnumName {
 static const EnumName kKspTypes[] = {{"cg", PB_KSP_CG}, {"preonly", PB_KSP_PREONLY},
                                      {"richardson", PB_KSP_RICHARDSON},
                                      {"chebyshev", PB_KSP_CHEBYSHEV},
-                                     {"fgmres", PB_KSP_FGMRES}, {nullptr, 0}};
+                                     {"fgmres", PB_KSP_FGMRES}, {"pipecg", PB_KSP_PIPECG},
+                                     {nullptr, 0}};
 static const EnumName kPcTypes[] = {{"none", PB_PC_NONE}, {"jacobi", PB_PC_JACOBI},
                                     {"sor", PB_PC_SOR}, {"mg", PB_PC_MG}, {"gamg", PB_PC_MG},
                                     {"fft", PB_PC_FFT}, {nullptr, 0}};

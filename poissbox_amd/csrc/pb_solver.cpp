@@ -1,8 +1,8 @@
 // pb_solver.cpp -- KSP (KSPSolve_CG analogue) host logic: pb_ksp_create / begin / iterate / end /
 // solve / destroy, the CG enqueue paths and pb_solve*. The operator is in pb_op.cpp, the options in
 // pb_options.cpp, -ksp_type richardson | chebyshev | preonly in pb_ksp_stationary.cpp, fgmres in
-// pb_ksp_fgmres.cpp, the projected initial guess in pb_ksp_guess.cpp, -ksp_norm_type in pb_norm_type.cpp; struct pb_ksp
-// and what they share in pb_ksp.hpp.
+// pb_ksp_fgmres.cpp, pipecg in pb_ksp_pipecg.cpp, the projected initial guess in pb_ksp_guess.cpp,
+// -ksp_norm_type in pb_norm_type.cpp; struct pb_ksp and what they share in pb_ksp.hpp.
 //
 // The CG iteration runs as 2 fused stencil passes + 2 one-block finalize kernels per iteration
 // (plus a plane-sized boundary kernel and, on several ranks, one halo exchange and two scalar
@@ -73,11 +73,12 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
   if (check_ref_norm_opts(&k->opts) != PB_OK) return fail(PB_ERR_ARG);
   const int kt = k->opts.ksp_type;
   if (kt != PB_KSP_CG && kt != PB_KSP_PREONLY && kt != PB_KSP_RICHARDSON &&
-      kt != PB_KSP_CHEBYSHEV && kt != PB_KSP_FGMRES)
+      kt != PB_KSP_CHEBYSHEV && kt != PB_KSP_FGMRES && kt != PB_KSP_PIPECG)
     return fail(set_error(PB_ERR_UNSUPPORTED, "unknown ksp_type %d", kt));
   pb_ksp_chebyshev_opts_default(&k->ch.opts);
   pb_pc_mg_opts_default(&k->mgopts);
   if (const int rc = fgmres_create(k)) return fail(rc);
+  if (const int rc = pipecg_create(k)) return fail(rc);
   if (check_richardson_scale(k->opts.richardson_scale) != PB_OK) return fail(PB_ERR_ARG);
   if (kt == PB_KSP_PREONLY &&
       (k->opts.initial_guess_nonzero || k->opts.guess_type != PB_GUESS_NONE))
@@ -263,6 +264,9 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   } else if (k->fgmres()) {
     PB_HIP(hipMemcpyAsync(k->d_st, &st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
     PB_TRY(fgmres_begin(k, b, x));
+  } else if (k->pipecg()) {
+    PB_HIP(hipMemcpyAsync(k->d_st, &st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    PB_TRY(pipecg_begin(k, b, x));
   } else {
     PB_TRY(cg_begin(k, b, x, st));
   }
@@ -723,13 +727,15 @@ int pb_ksp_iterate(pb_ksp* k, int64_t iters) {
   PB_TRY(ensure_done_cap(k, k->host_iter + iters + 2));
   // one rank, Jacobi, fused operator: the finalize steps ride in the passes' prologues
   // (PB_CG_FOLD=0 keeps the separate finalize launches)
-  const bool fold = C >= 2 && !k->rich() && !k->fgmres() && fused_kind(k->A->kind) &&
+  const bool fold = C >= 2 && !k->rich() && !k->fgmres() && !k->pipecg() &&
+                    fused_kind(k->A->kind) &&
                     !k->stored_z() && tune("cg_fold", 1) != 0;
   const bool none = k->norm_none();
   int64_t n = 0;
   for (; n < iters && !k->stopped; ++n) {
     if (k->rich()) PB_TRY(enqueue_rich_iteration(k));
     else if (k->fgmres()) PB_TRY(enqueue_fgmres_iteration(k));
+    else if (k->pipecg()) PB_TRY(enqueue_pipecg_iteration(k));
     else if (k->sr.on) PB_TRY(enqueue_sr_iteration(k, fold, n));
     else PB_TRY(enqueue_iteration(k, fold, fold && n > 0));
     const int64_t hi = k->host_iter++;
@@ -865,6 +871,7 @@ int pb_ksp_destroy(pb_ksp* k) {
   field_free(k->ri.x2);
   field_free(k->ri.x3);
   fgmres_destroy(k);
+  pipecg_destroy(k);
   if (k->mg) mg_destroy(k->mg);
   fftpc_destroy(k->fft);
   if (k->fg) {

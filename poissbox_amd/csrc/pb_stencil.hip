@@ -480,6 +480,79 @@ struct FgEpi {
   }
 };
 
+// Pipelined CG (-ksp_type pipecg) on the 7-point operator with Jacobi / no PC:
+// the whole iteration in one pass. The field is the preconditioned vector m = dinv w + shift,
+// formed on load from w (the shift follows from sum w, one of the five sums of the iteration's one
+// reduction: pcg_shift / fg_z in pb_device.hpp are the one definition, so pcg_pcshift_kernel and
+// the standalone operator give the same bits); the engine's Laplacian is n = A m (reference
+// summation order). The epilogue reads z, q, s, p, x, r, u and w at the point, takes m from the
+// z-queue's centre, performs the eight updates (pcg_update) with the state's alpha and beta and
+// accumulates the five sums of the new values. z, q, s, p, x, r, u are updated in place: a point
+// is read and written by one lane. w_new goes to the other w buffer: neighbouring waves and
+// blocks still read w around this point. 64 B read, 64 B written per DoF.
+// Eight operand rows of a 4-row tile are 64 doubles: prefetching them one plane ahead (as PassB
+// does with up to 5) would double that and leave the registers of the file; they are loaded in
+// the plane's own step, ahead of the z-queue's loads, and no 8-row tiles (WIDE8) are used.
+template <bool SHIFT>
+struct PcgLoad {
+  static constexpr int NR = 1;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ w;
+  const PcgState* ps;
+  const CgState* st;
+  double dinv = 1.0, shift = 0.0;
+  __device__ __forceinline__ void prepare() {
+    dinv = st->dinv;
+    if constexpr (SHIFT) shift = pcg_shift(dinv, ps->sums[4], st->ntot);
+  }
+  __device__ __forceinline__ const double* src(int) const { return w; }
+  __device__ __forceinline__ double value(const double* raw) const {
+    return fg_z<SHIFT>(raw[0], dinv, shift);
+  }
+};
+struct PcgEpi {
+  static constexpr int NS = kPcgSums, NE = 8;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true;
+  static constexpr bool PREFETCH = false;
+  PcgVecs v;
+  const PcgState* ps;
+  const CgState* st;
+  double alpha = 0.0, beta = 0.0;
+  bool first = false;
+  __device__ __forceinline__ void prepare() {
+    alpha = ps->alpha;
+    beta = ps->beta;
+    first = st->it == 0;
+  }
+  __device__ __forceinline__ const double* src(int a) const {
+    return a == 0 ? v.z
+                  : (a == 1 ? v.q
+                            : (a == 2 ? v.s
+                                      : (a == 3 ? v.p
+                                                : (a == 4 ? v.x
+                                                          : (a == 5 ? v.r : (a == 6 ? v.u : v.w))))));
+  }
+  // c = m, w = n at the point
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[NE][V], double* acc, int nt) const {
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      pcg_update(first, alpha, beta, c[e], w[e], op[0][e], op[1][e], op[2][e], op[3][e], op[4][e],
+                 op[5][e], op[6][e], op[7][e], acc);
+    store_row<V>(v.z, idx, op[0], nt);
+    store_row<V>(v.q, idx, op[1], nt);
+    store_row<V>(v.s, idx, op[2], nt);
+    store_row<V>(v.p, idx, op[3], nt);
+    store_row<V>(v.x, idx, op[4], nt);
+    store_row<V>(v.r, idx, op[5], nt);
+    store_row<V>(v.u, idx, op[6], nt);
+    store_row<V>(v.w_out, idx, op[7], nt);
+  }
+};
+
 // The Jacobi-type level smoothers of the multigrid (-mg_levels_pc_type jacobi under richardson or
 // chebyshev, pb_mg.hip): one smoothing step and its residual in one pass. The field is
 //   y_new = omega ((y - yp) + scale (dinv r)) + yp,
@@ -1018,6 +1091,90 @@ static int launch_any(pb_grid* g, const Star& s, const Load& ld, const StencilPl
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// An engine epilogue run from stored fields: the centre value c and the Laplacian w come from two
+// arrays instead of the z-queue, in the engine's tiles, z-chunks and per-lane order of
+// accumulation (launch_any's choice of V and TY, make_geo's chunks, block_partials), so the
+// partial sums -- and with them everything the next finalize computes -- are the bits of the
+// engine pass with the same epilogue. No neighbour is read: any slab, split grids included.
+// ---------------------------------------------------------------------------------------------
+template <int V, int TY, class Epi>
+__global__ __launch_bounds__(kThreads) void tiled_epi_kernel(Geo g, const double* __restrict__ cf,
+                                                             const double* __restrict__ wf, Epi ep0,
+                                                             double* parts,
+                                                             const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  Epi ep = ep0;
+  ep.prepare();
+  constexpr int NS = Epi::NS, NE = Epi::NE;
+  double acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) acc[s] = 0.0;
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int b = xcd_block(g.remap);
+  const int seg = b % g.nsegx;
+  b /= g.nsegx;
+  const int tile = b % g.ntile;
+  const int chunk = b / g.ntile;
+  const int j0 = (tile * kWaves + wid) * TY;
+  const int kb = g.k_lo + chunk * g.kstride;
+  const int ke = min(kb + g.kc, g.k_hi);
+  const int i0 = seg * 64 * V + lane * V;
+  if (i0 < g.nx && j0 < g.ny) {
+    const unsigned boff = (unsigned)i0 * 8u;
+    for (int k = kb; k < ke; ++k) {
+      const int64_t base = (int64_t)k * g.plane;
+#pragma unroll
+      for (int t = 0; t < TY; ++t) {
+        const RowIx ix{base + (int64_t)(j0 + t) * g.nx, boff};
+        double c[V], w[V], op[NE][V];
+        load_row_nt<V>(cf, ix, c);
+        load_row_nt<V>(wf, ix, w);
+#pragma unroll
+        for (int a = 0; a < NE; ++a) load_row_nt<V>(ep.src(a), ix, op[a]);
+        ep.template put<V>(ix, c, w, op, acc, g.nt);
+      }
+    }
+  }
+  block_partials<NS>(acc, parts);
+}
+
+template <int V, int TY, class Epi>
+static int launch_tiled_t(pb_grid* g, const double* cf, const double* wf, const Epi& ep,
+                          const int* skip, int* nb_out) {
+  Geo geo = make_geo(g, V, TY, PLANES_ALL, 0, Epi::WGCU, tune("engine_kc_skew", 0));
+  const int64_t nblocks = (int64_t)geo.nsegx * geo.ntile * geo.nchunk;
+  if (nblocks * Epi::NS > g->ctx->partials_cap)
+    return set_error(PB_ERR_UNSUPPORTED, "tiled grid of %lld blocks exceeds partials capacity",
+                     (long long)nblocks);
+  hipLaunchKernelGGL((tiled_epi_kernel<V, TY, Epi>), dim3((unsigned)nblocks), dim3(kThreads), 0,
+                     g->ctx->stream, geo, cf, wf, ep, g->ctx->d_partials, skip);
+  PB_HIP(hipGetLastError());
+  *nb_out = (int)nblocks;
+  return PB_OK;
+}
+
+// launch_any's tile shape for an epilogue without the WIDE8 / TALL traits
+template <class Epi>
+static int launch_tiled(pb_grid* g, const double* cf, const double* wf, const Epi& ep,
+                        const int* skip, int* nb_out) {
+  static_assert(!Wide8Of<Epi>::v && !TallOf<Epi>::v, "launch_any would choose 8-row tiles");
+  const bool vec2 = (g->n[0] % 2) == 0;
+  const int ty = pick_ty((int)g->n[1]);
+  if (vec2) {
+    switch (ty) {
+      case 4: return launch_tiled_t<2, 4>(g, cf, wf, ep, skip, nb_out);
+      case 2: return launch_tiled_t<2, 2>(g, cf, wf, ep, skip, nb_out);
+      default: return launch_tiled_t<2, 1>(g, cf, wf, ep, skip, nb_out);
+    }
+  }
+  switch (ty) {
+    case 4: return launch_tiled_t<1, 4>(g, cf, wf, ep, skip, nb_out);
+    case 2: return launch_tiled_t<1, 2>(g, cf, wf, ep, skip, nb_out);
+    default: return launch_tiled_t<1, 1>(g, cf, wf, ep, skip, nb_out);
+  }
+}
+
 // Timer names: a whole-grid launch is "<name>"; the two launches of a split apply (interior
 // planes, then the boundary planes after the halo exchange) are "<name>_interior" and
 // "<name>_boundary", and the caller times the apply as a whole under "<name>" (pb_solver.cpp),
@@ -1416,6 +1573,25 @@ int launch_fg_fused(pb_grid* g, const Star& s, const double* wt, double* v, doub
   const FgEpi ep{v, z, w_out, wt, fs};
   if (nullspace) return launch_any(g, s, FgLoad<true>{wt, fs, st}, gp, ep, &st->done);
   return launch_any(g, s, FgLoad<false>{wt, fs, st}, gp, ep, &st->done);
+}
+
+// Pipelined CG's iteration pass (PcgLoad / PcgEpi), whole grid, wrap planes, and the same
+// epilogue from stored m and n; always an iteration's launch (exits at entry once the state is
+// done). The five sums per block go to ctx->d_partials (*nparts blocks)
+int launch_pcg_fused(pb_grid* g, const Star& s, const PcgVecs& v, const PcgState* ps,
+                     const CgState* st, bool nullspace, int* nparts) {
+  ScopedTimer tm(g->ctx, "pipecg_pass");
+  const StencilPlanes gp = wrap_planes();
+  const PcgEpi ep{v, ps, st};
+  if (nullspace)
+    return launch_any(g, s, PcgLoad<true>{v.w, ps, st}, gp, ep, &st->done, PLANES_ALL, 0, nparts);
+  return launch_any(g, s, PcgLoad<false>{v.w, ps, st}, gp, ep, &st->done, PLANES_ALL, 0, nparts);
+}
+
+int launch_pcg_update(pb_grid* g, const double* m, const double* n, const PcgVecs& v,
+                      const PcgState* ps, const CgState* st, int* nparts) {
+  ScopedTimer tm(g->ctx, "pipecg_update");
+  return launch_tiled(g, m, n, PcgEpi{v, ps, st}, &st->done, nparts);
 }
 
 // Chebyshev's update + residual pass for updates i >= 1 (ChebLoad / RichEpi), whole grid, wrap

@@ -11,6 +11,7 @@
 !   -ksp_type chebyshev -pc_type mg                      (bounds estimated)
 !   -ksp_type chebyshev -ksp_chebyshev_eigenvalues 0.05,2.0 -ksp_chebyshev_esteig_steps 20
 !   -ksp_type fgmres -pc_type mg -ksp_gmres_restart 10   (restarted flexible GMRES)
+!   -ksp_type pipecg -pc_type mg                         (pipelined CG: one reduction per iteration)
 !   -pc_type mg -mg_levels_ksp_type chebyshev -mg_levels_pc_type jacobi -mg_levels_ksp_max_it 2
 program poissbox_demo
 
