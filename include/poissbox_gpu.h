@@ -615,6 +615,25 @@ int pb_compact_lapl(pb_grid* grid, const double dx[3], const pb_vec* f, pb_vec* 
  * App. D) with PCR line solves in LDS: ~80 B/DoF instead of 16 line-solve families; agrees with
  * pb_compact_lapl to rounding. This is what PB_OP_COMPACT applies inside CG. */
 int pb_compact_lapl_fast(pb_grid* grid, const double dx[3], const pb_vec* f, pb_vec* out);
+/* Bandwidth-oriented grad, div and interp: the same factorisation into line passes, one half
+ * operator (explicit RHS + one (alpha, 1, alpha) solve) per axis, register line solves where the
+ * line length is 64*{1,2,3,4,6,8,12,16} and the LDS-PCR kernel otherwise. Arguments and staggering
+ * as pb_compact_grad / pb_compact_div / pb_compact_interp (interp_div is stagger +1). They match
+ * the reference to rounding, NOT to the bit (operation order differs); the bit-exact calls above
+ * stay as they are. They accept every grid pb_compact_lapl_fast accepts and return its errors
+ * beyond; inputs must not alias outputs and the three components must be distinct vectors
+ * (PB_ERR_ARG). On a split grid the Z pass runs on y-slabs (all-to-all transposes) and every
+ * rank's slab is bit-identical to the one-rank result. N = the grid's local size; on a split
+ * grid each call also takes three y-slab fields and the transpose staging from the context.
+ *   pb_compact_grad_fast   replaces src/compact_schemes.f90:42-88;  Z -> Y -> X, 112 B/DoF,
+ *                          context scratch 2N (the X passes run in place in df)
+ *   pb_compact_div_fast    replaces src/compact_schemes.f90:207-257; X -> Y -> Z, 112 B/DoF,
+ *                          context scratch 5N
+ *   pb_compact_interp_fast replaces src/compact_schemes.f90:93-152;  Z -> Y -> X, 48 B/DoF,
+ *                          context scratch N */
+int pb_compact_grad_fast(pb_grid* grid, const double dx[3], const pb_vec* f, pb_vec* const df[3]);
+int pb_compact_div_fast(pb_grid* grid, const double dx[3], const pb_vec* const f[3], pb_vec* df);
+int pb_compact_interp_fast(pb_grid* grid, int stagger, const pb_vec* f, pb_vec* fi);
 /* 1-D line operators on device arrays, batched like pb_tdma_batched (grad_1d/div_1d/interp_1d/
  * interp_1d_div: kind 0 = derivative, 1 = interpolation). */
 int pb_compact_1d_batched(pb_ctx* ctx, int kind, int stagger, double dx, int64_t n,

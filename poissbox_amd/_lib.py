@@ -161,6 +161,9 @@ _SIGS = {
     "pb_compact_interp": [c_p, C.c_int, c_p, c_p],
     "pb_compact_lapl": [c_p, P_d, c_p, c_p],
     "pb_compact_lapl_fast": [c_p, P_d, c_p, c_p],
+    "pb_compact_grad_fast": [c_p, P_d, c_p, C.POINTER(c_p)],
+    "pb_compact_div_fast": [c_p, P_d, C.POINTER(c_p), c_p],
+    "pb_compact_interp_fast": [c_p, C.c_int, c_p, c_p],
     "pb_compact_1d_batched": [c_p, C.c_int, C.c_int, c_d, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
     "pb_tdma_sweeps_batched": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, C.c_int],
     "pb_tdma_sweeps_batched_host": [c_p, c_i64, c_i64, c_i64, c_i64, P_d, P_d, P_d, P_d,

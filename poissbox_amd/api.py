@@ -746,3 +746,23 @@ def compact_lapl_fast(da, dx, f, out):
     """3-pass factorised compact Laplacian with PCR line solves (agrees with compact_lapl to
     rounding); the operator PB_OP_COMPACT applies."""
     L.call("pb_compact_lapl_fast", da.h, _d_3(dx), f.h, out.h)
+
+
+def compact_grad_fast(da, dx, f, df3):
+    """compact_grad by factorised half-operator line passes (112 B/DoF; agrees with compact_grad
+    to rounding). f must not be one of df3, and the three df3 must be distinct."""
+    arr = (C.c_void_p * 3)(*[v.h.value for v in df3])
+    L.call("pb_compact_grad_fast", da.h, _d_3(dx), f.h, arr)
+
+
+def compact_div_fast(da, dx, f3, df):
+    """compact_div by factorised half-operator line passes (112 B/DoF; agrees with compact_div
+    to rounding). df must not be one of f3, and the three f3 must be distinct."""
+    arr = (C.c_void_p * 3)(*[v.h.value for v in f3])
+    L.call("pb_compact_div_fast", da.h, _d_3(dx), arr, df.h)
+
+
+def compact_interp_fast(da, stagger, f, fi):
+    """compact_interp by three half-operator line passes (48 B/DoF; agrees with compact_interp
+    to rounding)."""
+    L.call("pb_compact_interp_fast", da.h, int(stagger), f.h, fi.h)

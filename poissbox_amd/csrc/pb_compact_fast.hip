@@ -42,6 +42,7 @@ struct Term {
   int op;  // 0 = J, 1 = L
   int in;  // input index
   int out; // output index
+  int half = 0;  // 0: the full operator; -1 / +1: its half at that stagger alone (grad / div / interp)
 };
 struct FastPass {
   int n;          // line length
@@ -189,6 +190,16 @@ __global__ __launch_bounds__(kFT) void compact_fast_kernel(FastPass p) {
       loaded = tm.in;
     }
     const Half& h = p.ops[tm.op].h;
+    if (tm.half) {  // one half operator: RHS + solve at its stagger
+      rhs(h, tm.half < 0 ? 0 : 1);
+      solve(h.pcr);
+#pragma unroll
+      for (int m = 0; m < kFC; ++m) {
+        if (tm.out == 0) acc[0][m] += d[m];
+        else acc[1][m] += d[m];
+      }
+      continue;
+    }
     rhs(h, 0);     // stagger -1 (cell -> vertex)
     solve(h.pcr);
     double keep[kFC];
@@ -312,6 +323,40 @@ int compact_pass_x(pb_ctx* ctx, const int64_t d[3], double h, const double* s_, 
   p.in[1] = t;
   p.out[0] = out;
   p.nout = 1;
+  return launch_pass(ctx, p);
+}
+
+// One half-operator pass (grad / div / interp, pb_compact_ops.hip) on the LDS-PCR kernel:
+// out0 = H(k0) in0 [+ H(k1) in1], optionally out1 = H(k1) in0, every H once at `stagger`.
+// An X pass (lines contiguous, layout 1) may run in place: a block reads its whole lines first.
+int compact_half_pass_pcr(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
+                          const HalfPass& a) {
+  const int64_t nx = d[0], ny = d[1], nz = d[2];
+  const int64_t n = d[axis];
+  if (n > kTile) return set_error(PB_ERR_UNSUPPORTED, "compact fast path: n > %d", kTile);
+  FastPass p{};
+  p.n = (int)n;
+  if (axis == 2) {  // lines along k; tile = consecutive i for fixed j
+    p.layout = 0, p.ninner = (int)nx, p.nouter = (int)ny;
+    p.li = 1, p.lo = nx, p.es = nx * ny;
+  } else if (axis == 1) {  // lines along j; tile = consecutive i for fixed k
+    p.layout = 0, p.ninner = (int)nx, p.nouter = (int)nz;
+    p.li = 1, p.lo = nx * ny, p.es = nx;
+  } else {  // lines along i (contiguous); tile = consecutive j for fixed k
+    p.layout = 1, p.ninner = (int)ny, p.nouter = (int)nz;
+    p.li = nx, p.lo = nx * ny, p.es = 1;
+  }
+  p.ops[0] = make_op(0, n, h);
+  p.ops[1] = make_op(1, n, h);
+  p.in[0] = a.in0;
+  p.in[1] = a.in1;
+  p.out[0] = a.out0;
+  p.out[1] = a.out1;
+  p.nout = a.out1 ? 2 : 1;
+  p.nterms = 1;
+  p.term[0] = Term{a.k0, 0, 0, stagger};
+  if (a.in1) p.term[p.nterms++] = Term{a.k1, 1, 0, stagger};
+  if (a.out1) p.term[p.nterms++] = Term{a.k1, 0, 1, stagger};
   return launch_pass(ctx, p);
 }
 

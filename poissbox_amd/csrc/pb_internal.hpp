@@ -517,6 +517,21 @@ int compact_pass_y(pb_ctx* ctx, const int64_t d[3], double h, const double* u, c
                    double* s, double* t, const YSlabPlan* blk_in = nullptr);
 int compact_pass_x(pb_ctx* ctx, const int64_t d[3], double h, const double* s, const double* t,
                    double* out);
+// ---- half-operator line passes: the factorised grad / div / interp (pb_compact_ops.hip) ----
+// out0 = H(k0) in0 [+ H(k1) in1], optionally out1 = H(k1) in0 (never both); H(0) = interp_1d,
+// H(1) = grad_1d (h), every H applied once at the call's stagger along `axis` of the box d
+struct HalfPass {
+  int k0 = 0, k1 = 0;
+  const double* in0 = nullptr;
+  const double* in1 = nullptr;
+  double* out0 = nullptr;
+  double* out1 = nullptr;
+};
+// register line solves where n = 64*C supports them, else the LDS-PCR kernel
+int compact_half_pass(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
+                      const HalfPass& a);
+int compact_half_pass_pcr(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
+                          const HalfPass& a);
 // ---- multi-rank Z pass: z-slab <-> y-slab all-to-all transposes (compact_dist.cpp) ----
 int64_t compact_dist_work_len(const pb_grid* g);
 // plan_out != nullptr: on equal 2^k-row y-slabs u, v are left in the all-to-all layout (the plan

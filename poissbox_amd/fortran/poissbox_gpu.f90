@@ -111,6 +111,7 @@ module poissbox_gpu
   public :: PoissboxContext, PoissboxCommRank, PoissboxAllreduceSum, PoissboxBarrier
   public :: assemble_laplacian
   public :: CompactGrad, CompactDiv, CompactInterp, CompactLapl, CompactLaplFast
+  public :: CompactGradFast, CompactDivFast, CompactInterpFast
   ! C entry points on device pointers / host arrays (batched line solvers, compact operators)
   public :: c_pb_comm_unique_id, c_pb_tdma_batched, c_pb_tdma_sweeps_batched
   public :: c_pb_pcr_alpha_batched, c_pb_compact_1d_batched
@@ -309,6 +310,27 @@ module poissbox_gpu
        import :: c_int, c_ptr, c_double
        type(c_ptr), value :: grid, f, out
        real(c_double), dimension(3) :: dx
+     end function
+     ! the factorised grad / div / interp (half-operator line passes; rounding-level agreement)
+     integer(c_int) function c_pb_compact_grad_fast(grid, dx, f, df) &
+          bind(C, name="pb_compact_grad_fast")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: grid, f
+       real(c_double), dimension(3) :: dx
+       type(c_ptr), dimension(3) :: df
+     end function
+     integer(c_int) function c_pb_compact_div_fast(grid, dx, f, df) &
+          bind(C, name="pb_compact_div_fast")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: grid, df
+       real(c_double), dimension(3) :: dx
+       type(c_ptr), dimension(3) :: f
+     end function
+     integer(c_int) function c_pb_compact_interp_fast(grid, stagger, f, fi) &
+          bind(C, name="pb_compact_interp_fast")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: grid, f, fi
+       integer(c_int), value :: stagger
      end function
      integer(c_int) function c_pb_ctx_destroy(ctx) bind(C, name="pb_ctx_destroy")
        import :: c_int, c_ptr
@@ -766,6 +788,46 @@ contains
     ierr = c_pb_compact_lapl_fast(da%h, d, f%h, out%h)
     call check(ierr, "CompactLaplFast")
   end subroutine CompactLaplFast
+
+  !! the factorised grad / div / interp (src/compact_schemes.f90:42-88, :207-257, :93-152 to
+  !! rounding): f must not alias df, the three components must be distinct vectors
+  subroutine CompactGradFast(da, dx, f, df, ierr)
+    type(tDM), intent(in) :: da
+    real(pb_dp), dimension(3), intent(in) :: dx
+    type(tVec), intent(in) :: f
+    type(tVec), dimension(3), intent(inout) :: df
+    integer, intent(out) :: ierr
+    real(c_double), dimension(3) :: d
+    type(c_ptr), dimension(3) :: h
+    d = dx
+    h = [df(1)%h, df(2)%h, df(3)%h]
+    ierr = c_pb_compact_grad_fast(da%h, d, f%h, h)
+    call check(ierr, "CompactGradFast")
+  end subroutine CompactGradFast
+
+  subroutine CompactDivFast(da, dx, f, df, ierr)
+    type(tDM), intent(in) :: da
+    real(pb_dp), dimension(3), intent(in) :: dx
+    type(tVec), dimension(3), intent(in) :: f
+    type(tVec), intent(inout) :: df
+    integer, intent(out) :: ierr
+    real(c_double), dimension(3) :: d
+    type(c_ptr), dimension(3) :: h
+    d = dx
+    h = [f(1)%h, f(2)%h, f(3)%h]
+    ierr = c_pb_compact_div_fast(da%h, d, h, df%h)
+    call check(ierr, "CompactDivFast")
+  end subroutine CompactDivFast
+
+  subroutine CompactInterpFast(da, stagger, f, fi, ierr)
+    type(tDM), intent(in) :: da
+    integer, intent(in) :: stagger
+    type(tVec), intent(in) :: f
+    type(tVec), intent(inout) :: fi
+    integer, intent(out) :: ierr
+    ierr = c_pb_compact_interp_fast(da%h, int(stagger, c_int), f%h, fi%h)
+    call check(ierr, "CompactInterpFast")
+  end subroutine CompactInterpFast
 
   subroutine PoissboxFinalize(ierr)
     integer, intent(out) :: ierr
