@@ -1,5 +1,5 @@
 // pb_cg_device.hpp -- device-side CG scalar logic shared by the stencil engine's fused passes
-// (pb_stencil.hip) and the single-reduction one-pass kernel (pb_cg_sr.hip): PETSc KSPSolve_CG /
+// (pb_star7.hpp, pb_cg_passes.hip) and the single-reduction one-pass kernel (pb_cg_sr.hip): PETSc KSPSolve_CG /
 // KSPSolve_CG_SingleReduction stages on a register copy of CgState, the fixed-order reduction of
 // per-block partial sums, and the finalize folded into a pass prologue (Fold).
 #pragma once

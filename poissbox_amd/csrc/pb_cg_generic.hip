@@ -1,6 +1,6 @@
 // pb_cg_generic.hip -- CG iteration kernels for operators / preconditioners without a fused
 // stencil engine (the compact Laplacian as A, SOR / multigrid as PC). Same device-resident scalar
-// logic (cg_finalize_kernel in pb_stencil.hip) as the fused 7-point path.
+// logic (cg_finalize_kernel in pb_cg_passes.hip) as the fused 7-point path.
 #include "pb_internal.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void cg_pc_sums_kernel(const double* __restric
 // setup from a nonzero initial guess where no stencil engine forms A x0 (compact / assembled A) or
 // the PC stores z (SOR / MG / FFT): w = A x0 came from the operator; r = b - w, p = 0, x0 left
 // alone. SUMS (Jacobi / no PC): the setup's four sums of s = dinv r and the two of dinv b behind
-// the stopping reference ||N(M^-1 b)||, as the fused pass takes them (GuessInit, pb_stencil.hip)
+// the stopping reference ||N(M^-1 b)||, as the fused pass takes them (GuessInit, pb_cg_passes.hip)
 // SUMS = 2 (-ksp_norm_type unpreconditioned with a stored-z PC): sum r^2 and sum b^2 -- ||r_0||
 // and the reference ||b|| without a PC application
 template <int SUMS>

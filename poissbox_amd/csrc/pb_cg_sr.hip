@@ -1,7 +1,7 @@
 // pb_cg_sr.hip -- the single-reduction CG iteration (PETSc KSPSolve_CG_SingleReduction,
 // -ksp_cg_single_reduction) as ONE pass over the grid per iteration (one rank).
 //
-// The two-pass form (pb_stencil.hip: pass P forms p, w = A p and r' = r - alpha w; pass S forms
+// The two-pass form (pb_cg_passes.hip: pass P forms p, w = A p and r' = r - alpha w; pass S forms
 // t = dinv r' - mu and s = A t for the sums) reads r' a second time. Here one z-march does both:
 // a wave forms p one plane ahead of w and w one plane ahead of s,
 //   step k:  p(k+2) = (dinv r - mu) + b p_old          (pointwise, stored)

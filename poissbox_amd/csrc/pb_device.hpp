@@ -1,4 +1,4 @@
-// pb_device.hpp -- device-side helpers shared by the stencil engine (pb_stencil.hip) and the
+// pb_device.hpp -- device-side helpers shared by the stencil engine (pb_star7.hpp) and the
 // fused multigrid sweeps (pb_mg_sweep.hip): 16-byte row loads/stores, DPP wave shifts, the
 // deterministic block reduction of partial sums, the XCD-aware block order.
 #pragma once
@@ -127,9 +127,9 @@ __device__ __forceinline__ void store_pts(__amdgpu_buffer_rsrc_t rs, unsigned of
 
 // ---------------------------------------------------------------------------------------------
 // The update step of the stationary iterations, defined once: Richardson and Chebyshev as KSPs
-// (RichLoad / ChebLoad in pb_stencil.hip, rich_x_kernel / cheb_x_kernel in pb_ksp_stationary.hip)
-// and as the multigrid's Jacobi-type level smoothers (PolyLoad<N> in pb_stencil.hip, poly_value<N>
-// in pb_mg.hip). Every operation is rounded, in the order written here (no FMA contraction: the
+// (RichLoad / ChebLoad, rich_x_kernel / cheb_x_kernel in pb_ksp_stationary.hip)
+// and as the multigrid's Jacobi-type level smoothers (PolyLoad<N> in pb_mg_engine.hip,
+// poly_value<N> in pb_mg.hip). Every operation is rounded, in the order written here (no FMA contraction: the
 // build's -ffp-contract=off), so the fused engine passes and the vector kernels give the same
 // bits. SHIFT = false (the multigrid forms: no null-space shift): the add is absent, not + 0.0,
 // which would turn a -0.0 into +0.0.
@@ -159,7 +159,7 @@ __device__ __forceinline__ double cheb_step(double y, double ym1, double q, doub
   t = omega * t;
   return t + ym1;
 }
-// FGMRES on Jacobi / no PC (pb_ksp_fgmres.hip, FgLoad in pb_stencil.hip): the preconditioned
+// FGMRES on Jacobi / no PC (pb_ksp_fgmres.hip: its kernels and FgLoad): the preconditioned
 // direction z = dinv (s wt) + shift from the unnormalised wt, v = s wt being the basis vector
 template <bool SHIFT>
 __device__ __forceinline__ double fg_z(double v, double dinv, double shift) {
@@ -167,7 +167,7 @@ __device__ __forceinline__ double fg_z(double v, double dinv, double shift) {
   if constexpr (SHIFT) z = z + shift;
   return z;
 }
-// Pipelined CG (pb_ksp_pipecg.hip, PcgLoad / PcgEpi in pb_stencil.hip). The preconditioned
+// Pipelined CG (pb_ksp_pipecg.hip: its kernels and PcgLoad / PcgEpi). The preconditioned
 // vector is m = fg_z(w, dinv, shift) with the null-space shift from the sum of what the PC is
 // applied to (Jacobi / no PC: sum w, which rides in the iteration's one reduction) or, with
 // dinv = 1, from the sum of a stored M^-1 w: -((dinv sum) / ntot)

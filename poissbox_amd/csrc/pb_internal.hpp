@@ -261,7 +261,8 @@ int launch_comm_stall(pb_ctx* ctx, hipStream_t s, int ms);
       return ::pb::set_error(PB_ERR_COMM, "communication failed earlier on this context");  \
   } while (0)
 
-// ---- kernels (pb_stencil.hip) ----
+// ---- the stencil engine's passes (engine: pb_star7.hpp; the operator apply: pb_stencil.hip; the
+// CG passes: pb_cg_passes.hip; multigrid's: pb_mg_engine.hip) ----
 struct StencilPlanes {
   const double* ghost_lo;  // plane at k = -1
   const double* ghost_hi;  // plane at k = nzl
@@ -278,6 +279,10 @@ inline StencilPlanes wrap_planes() {
 }
 inline Star star_of(const pb_op* op) { return Star{op->cx, op->cy, op->cz, op->cc}; }
 enum { PLANES_ALL = 0, PLANES_INTERIOR = 1, PLANES_BOUNDARY = 2 };
+// the timer of a launch over the planes of `mode` (pb_stencil.hip)
+__attribute__((visibility("hidden"))) const char* timer_name(int mode, const char* all,
+                                                             const char* interior,
+                                                             const char* boundary);
 int launch_star7_apply(pb_grid* g, const Star& s, const double* x, double* y,
                        const StencilPlanes& gp, int mode);
 // assembled P (pb_assembled.hip): re-sum the seam and slab-boundary rows of y = P x in PETSc AIJ
@@ -290,7 +295,7 @@ struct CgState;
 int launch_mg_sor(pb_grid* g, const Star& s, double* x, const double* b, const StencilPlanes& gp,
                   double omega, int color, int first, const int* skip,
                   const CgState* sums_st = nullptr, int* nparts = nullptr);
-// both red-black half-sweeps (c1 first) in one pass, out of place, one rank (pb_stencil.hip)
+// both red-black half-sweeps (c1 first) in one pass, out of place, one rank (pb_mg_sweep.hip)
 bool sor_sweep2_supported(const pb_grid* g);
 int launch_sor_sweep2(pb_grid* g, const Star& s, const double* xin, const double* b, double* xout,
                       double omega, int c1, const int* skip, const CgState* sums_st = nullptr,
@@ -355,7 +360,7 @@ inline int rr_part_off(const pb_ctx* ctx, int ns) { return (int)(ctx->partials_c
 int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, CgState* st,
                    double dinv, double* hist, int* h_done);
 // Setup from a nonzero initial guess (-ksp_initial_guess_nonzero; x0 is never written):
-//  - fused operator, Jacobi / no PC: one engine pass (pb_stencil.hip GuessInit) reads x0 and b,
+//  - fused operator, Jacobi / no PC: one engine pass (pb_cg_passes.hip GuessInit) reads x0 and b,
 //    stores r = b - A x0 and p = 0, and takes six sums per block (the setup's four of dinv r,
 //    and dinv b, (dinv b)^2) into ctx->d_partials + part_off * 6;
 //  - elsewhere: w = A x0 by the operator, then launch_cg_guess_resid (pb_cg_generic.hip):
@@ -416,7 +421,7 @@ int launch_cg_pass_b(pb_grid* g, const Star& s, const double* p, const double* c
                      int* h_done, int64_t host_iter, int defer, bool finalize = true,
                      const PStore& ps = PStore{}, RrParts* rr = nullptr);
 int launch_cg_flush(pb_grid* g, double* x, const double* p, double alpha);
-// Folded single-rank Jacobi iteration (finalize in the passes' prologues, pb_stencil.hip): state
+// Folded single-rank Jacobi iteration (finalize in the passes' prologues, pb_cg_passes.hip): state
 // in two slots st2[0..1]; pass A of iteration host_iter >= 1 runs stage 2 of host_iter - 1
 // (st2[1] -> st2[0], history and done flag as finalize's), pass B stage 1 (st2[0] -> st2[1]);
 // cg_fold_tail completes the last iteration of a batch and leaves the state in st2[0].
@@ -432,7 +437,7 @@ int launch_cg_pass_b_folded(pb_grid* g, const Star& s, const double* p,
 int cg_fold_tail(pb_ctx* ctx, int nparts_b, CgState* st2, double* hist, int* h_done,
                  int64_t host_iter);
 // Single-reduction CG (PETSc KSPSolve_CG_SingleReduction, -ksp_cg_single_reduction), two engine
-// passes per iteration and ONE reduction (pb_stencil.hip):
+// passes per iteration and ONE reduction (pb_cg_passes.hip):
 //   pass P: prologue = [the previous iteration's residual-sum stage (folded, one rank)] + the top
 //     of the iteration (beta / betaold, p'w = delta - beta^2 dpiold / betaold^2, alpha); body:
 //     p = (dinv r - mu) + b p_old on load, w = A p, r_out = r - alpha w, store p and r_out, the
@@ -650,7 +655,7 @@ int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_
                      const RrParts& rr = RrParts{});
 
 // ---- stationary solves: -ksp_type richardson / preonly (pb_ksp_stationary.hip, and the engine
-// pass launch_rich_update in pb_stencil.hip) ----
+// pass launch_rich_update in pb_ksp_stationary.hip) ----
 // Richardson keeps CG's device-resident state (CgState: mu = the mean of the current M^-1 r,
 // it = its = updates done, dp, rnorm0, ttol, reason, done, nlog), history buffer and done flags.
 int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double* q,
@@ -681,7 +686,7 @@ int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst,
 int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
                   double* hist, int* h_done, int64_t host_iter, double cheb_mu = 0.0,
                   double cheb_omegaprod = 0.0, const RrParts& rr = RrParts{});
-// Chebyshev's update i >= 1 (pb_stencil.hip ChebLoad): y_out = omega ((y - ym1) + scale (dinv q -
+// Chebyshev's update i >= 1 (pb_ksp_stationary.hip ChebLoad): y_out = omega ((y - ym1) + scale (dinv q -
 // mean)) + ym1 with omega = st->alpha, r_out = b - A y_out, one rank, wrap planes; sums as
 // launch_rich_update's. Update 0 is launch_rich_update with Chebyshev's scale
 int launch_cheb_update(pb_grid* g, const Star& s, const double* y, const double* ym1,

@@ -247,7 +247,7 @@ int launch_fg_shift(pb_ctx* ctx, double* z, const FgState* fs, const CgState* st
 int launch_fg_pcshift(pb_ctx* ctx, const double* v, double* z, const FgState* fs,
                       const CgState* st, int64_t n, bool nullspace);
 // The engine pass of a step on the 7-point operator with Jacobi / no PC (one rank, wrap planes;
-// pb_stencil.hip FgLoad / FgEpi): from the unnormalised direction wt, v = fs->scale wt and
+// pb_ksp_fgmres.hip FgLoad / FgEpi): from the unnormalised direction wt, v = fs->scale wt and
 // z = dinv v + fs->shift formed on load; stores v and z and writes w_out = A z (another buffer
 // than wt). 8 B read, 24 B written per DoF; the bits of scale + pcshift + operator
 int launch_fg_fused(pb_grid* g, const Star& s, const double* wt, double* v, double* z,
@@ -311,7 +311,7 @@ int launch_pcg_sums(pb_ctx* ctx, const double* r, const double* u, const double*
 // update count advances first
 int launch_pcg_finalize(pb_ctx* ctx, CgState* st, PcgState* ps, const double* parts, int nparts,
                         double* hist, int* h_done, bool setup, int ref, int64_t host_iter);
-// ---- pb_stencil.hip ----
+// ---- pb_ksp_pipecg.hip: the update pass on the stencil engine (pb_star7.hpp) ----
 // The iteration on the 7-point operator with Jacobi / no PC (one rank, wrap planes; PcgLoad /
 // PcgEpi): m = dinv w + shift formed on load, n = A m, the eight updates and the five sums of the
 // new values; v.w_out is another buffer than v.w. 64 B read, 64 B written per DoF

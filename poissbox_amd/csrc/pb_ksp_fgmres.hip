@@ -2,7 +2,7 @@
 // a cycle (FgState, pb_ksp.hpp) with its one-thread kernels -- the cycle start, the Arnoldi step's
 // scalar part, the triangular solve -- and the field passes around them: the basis vector's
 // scaling, the Jacobi / identity preconditioner with its null-space shift (the 7-point operator
-// on one rank runs these two and the operator as one engine pass instead: pb_stencil.hip FgLoad),
+// on one rank runs these two and the operator as one engine pass instead: FgLoad below),
 // the sum and shift behind a stored-z preconditioner, and the solution build over the live
 // directions. The orthogonalisation itself is the multi-dot / multi-axpy pair of pb_guess.hip, the
 // operator and the stored-z preconditioners are the KSP's.
@@ -15,6 +15,7 @@
 #include "pb_ksp.hpp"
 #include "pb_device.hpp"
 #include "pb_cg_device.hpp"
+#include "pb_star7.hpp"
 
 namespace pb {
 
@@ -319,6 +320,78 @@ int launch_fg_build(pb_ctx* ctx, double* x, const FgTable& z, const FgState* fs,
                      fs, st, force ? 1 : 0, n);
   PB_HIP(hipGetLastError());
   return PB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The step-start pass on the stencil engine (pb_star7.hpp)
+// ---------------------------------------------------------------------------------------------
+// Flexible GMRES (-ksp_type fgmres) on the 7-point operator with Jacobi / no PC:
+// the start of an Arnoldi step in one pass. The field is the preconditioned direction
+// z = dinv (s wt) + shift, formed on load from the unnormalised direction wt the orthogonalisation
+// left (s = 1 / ||wt|| and the null-space shift are the state's: fg_step_kernel / fg_start_kernel
+// set them from the multi-axpy's sums), every product and sum rounded (fg_z in pb_device.hpp is
+// the one definition), so fg_scale_kernel + fg_pcshift_kernel (pb_ksp_fgmres.hip) and the
+// standalone operator give the same bits. The epilogue stores the basis vector v = s wt (wt read
+// again at the point: the z-queue holds z, not wt), the centre value z and w = A z (reference
+// summation order). Reads wt, writes v, z, w: 8 + 24 B/DoF against 48 for the three passes
+// (scale 16, preconditioner 16, operator 16). w goes to another buffer than wt: neighbouring
+// waves and blocks still read wt around this point. RichEpi's launch shape (two and more streams
+// written, non-temporal).
+template <bool SHIFT>
+struct FgLoad {
+  static constexpr int NR = 1;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ wt;
+  const FgState* fs;
+  const CgState* st;
+  double scale = 0.0, dinv = 1.0, shift = 0.0;
+  __device__ __forceinline__ void prepare() {
+    scale = fs->scale;
+    dinv = st->dinv;
+    shift = fs->shift;
+  }
+  __device__ __forceinline__ const double* src(int) const { return wt; }
+  __device__ __forceinline__ double value(const double* raw) const {
+    const double v = scale * raw[0];
+    return fg_z<SHIFT>(v, dinv, shift);
+  }
+};
+struct FgEpi {
+  static constexpr int NS = 0, NE = 1;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true, WIDE8 = true;
+  static constexpr bool PREFETCH = true;
+  double* __restrict__ v_out;
+  double* __restrict__ z_out;
+  double* __restrict__ w_out;
+  const double* __restrict__ wt;
+  const FgState* fs;
+  double scale = 0.0;
+  __device__ __forceinline__ void prepare() { scale = fs->scale; }
+  __device__ __forceinline__ const double* src(int) const { return wt; }
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[1][V], double* acc, int nt) const {
+    double vv[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) vv[e] = scale * op[0][e];
+    (void)acc;
+    store_row<V>(w_out, idx, w, nt);
+    store_row<V>(z_out, idx, c, nt);
+    store_row<V>(v_out, idx, vv, nt);
+  }
+};
+
+// FGMRES's step-start pass (FgLoad / FgEpi), whole grid, wrap planes; always an iteration's launch
+// (exits at entry once the state is done)
+int launch_fg_fused(pb_grid* g, const Star& s, const double* wt, double* v, double* z,
+                    double* w_out, const FgState* fs, const CgState* st, bool nullspace) {
+  ScopedTimer tm(g->ctx, "fgmres_fused");
+  const StencilPlanes gp = wrap_planes();
+  const FgEpi ep{v, z, w_out, wt, fs};
+  if (nullspace) return launch_any(g, s, FgLoad<true>{wt, fs, st}, gp, ep, Launch{&st->done});
+  return launch_any(g, s, FgLoad<false>{wt, fs, st}, gp, ep, Launch{&st->done});
 }
 
 }  // namespace pb

@@ -1,7 +1,7 @@
 // pb_ksp_pipecg.cpp -- the host part of -ksp_type pipecg: pipelined CG, PETSc
 // KSPSolve_PIPECG with PC_LEFT, kept on the device. pb_ksp_create's share, pb_ksp_begin's setup
-// and one iteration of pb_ksp_iterate. The kernels are in pb_ksp_pipecg.hip, the update pass in
-// pb_stencil.hip; the done flags, history and polling are CG's (pb_solver.cpp).
+// and one iteration of pb_ksp_iterate. The kernels and the update pass are in
+// pb_ksp_pipecg.hip; the done flags, history and polling are CG's (pb_solver.cpp).
 //
 //   r = b (x = 0) or b - A x0;  u = N(M^-1 r);  w = A u;  the five sums;  the finalize (i = 0)
 //   iteration i:  m = N(M^-1 w);  n = A m;  the eight updates with alpha_i, beta_i and the five

@@ -3,9 +3,9 @@
 // space. The small state (PcgState, pb_ksp.hpp) with its finalize kernel -- the one reduction of
 // an iteration, the norm logged and tested, beta and alpha -- and the field passes of the setup
 // and of the unfused iteration: the sum of a field, the Jacobi / identity preconditioner with its
-// null-space shift (the 7-point operator on one rank forms it on load instead: pb_stencil.hip
-// PcgLoad), the setup's five sums. The update pass itself runs in the stencil engine's tiles
-// (pb_stencil.hip: PcgEpi with the engine's Laplacian, or with a stored n), so that the fused and
+// null-space shift (the 7-point operator on one rank forms it on load instead: PcgLoad,
+// below), the setup's five sums. The update pass itself runs in the stencil engine's tiles
+// (pb_star7.hpp: PcgEpi with the engine's Laplacian, or with a stored n), so that the fused and
 // the unfused iteration sum their partials in one order and give the same bits.
 //
 // Breakdown: like PETSc's pipecg this has no indefinite-PC or indefinite-matrix test. A zero or
@@ -19,6 +19,7 @@
 #include "pb_ksp.hpp"
 #include "pb_device.hpp"
 #include "pb_cg_device.hpp"
+#include "pb_star7.hpp"
 
 namespace pb {
 
@@ -199,6 +200,102 @@ int launch_pcg_finalize(pb_ctx* ctx, CgState* st, PcgState* ps, const double* pa
                      nparts, hist, h_done, setup ? 1 : 0, ref, host_iter);
   PB_HIP(hipGetLastError());
   return PB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The iteration pass on the stencil engine (pb_star7.hpp)
+// ---------------------------------------------------------------------------------------------
+// Pipelined CG (-ksp_type pipecg) on the 7-point operator with Jacobi / no PC:
+// the whole iteration in one pass. The field is the preconditioned vector m = dinv w + shift,
+// formed on load from w (the shift follows from sum w, one of the five sums of the iteration's one
+// reduction: pcg_shift / fg_z in pb_device.hpp are the one definition, so pcg_pcshift_kernel and
+// the standalone operator give the same bits); the engine's Laplacian is n = A m (reference
+// summation order). The epilogue reads z, q, s, p, x, r, u and w at the point, takes m from the
+// z-queue's centre, performs the eight updates (pcg_update) with the state's alpha and beta and
+// accumulates the five sums of the new values. z, q, s, p, x, r, u are updated in place: a point
+// is read and written by one lane. w_new goes to the other w buffer: neighbouring waves and
+// blocks still read w around this point. 64 B read, 64 B written per DoF.
+// Eight operand rows of a 4-row tile are 64 doubles: prefetching them one plane ahead (as PassB
+// does with up to 5) would double that and leave the registers of the file; they are loaded in
+// the plane's own step, ahead of the z-queue's loads, and no 8-row tiles (WIDE8) are used.
+template <bool SHIFT>
+struct PcgLoad {
+  static constexpr int NR = 1;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ w;
+  const PcgState* ps;
+  const CgState* st;
+  double dinv = 1.0, shift = 0.0;
+  __device__ __forceinline__ void prepare() {
+    dinv = st->dinv;
+    if constexpr (SHIFT) shift = pcg_shift(dinv, ps->sums[4], st->ntot);
+  }
+  __device__ __forceinline__ const double* src(int) const { return w; }
+  __device__ __forceinline__ double value(const double* raw) const {
+    return fg_z<SHIFT>(raw[0], dinv, shift);
+  }
+};
+struct PcgEpi {
+  static constexpr int NS = kPcgSums, NE = 8;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true;
+  static constexpr bool PREFETCH = false;
+  PcgVecs v;
+  const PcgState* ps;
+  const CgState* st;
+  double alpha = 0.0, beta = 0.0;
+  bool first = false;
+  __device__ __forceinline__ void prepare() {
+    alpha = ps->alpha;
+    beta = ps->beta;
+    first = st->it == 0;
+  }
+  __device__ __forceinline__ const double* src(int a) const {
+    return a == 0 ? v.z
+                  : (a == 1 ? v.q
+                            : (a == 2 ? v.s
+                                      : (a == 3 ? v.p
+                                                : (a == 4 ? v.x
+                                                          : (a == 5 ? v.r : (a == 6 ? v.u : v.w))))));
+  }
+  // c = m, w = n at the point
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[NE][V], double* acc, int nt) const {
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      pcg_update(first, alpha, beta, c[e], w[e], op[0][e], op[1][e], op[2][e], op[3][e], op[4][e],
+                 op[5][e], op[6][e], op[7][e], acc);
+    store_row<V>(v.z, idx, op[0], nt);
+    store_row<V>(v.q, idx, op[1], nt);
+    store_row<V>(v.s, idx, op[2], nt);
+    store_row<V>(v.p, idx, op[3], nt);
+    store_row<V>(v.x, idx, op[4], nt);
+    store_row<V>(v.r, idx, op[5], nt);
+    store_row<V>(v.u, idx, op[6], nt);
+    store_row<V>(v.w_out, idx, op[7], nt);
+  }
+};
+
+// Pipelined CG's iteration pass (PcgLoad / PcgEpi), whole grid, wrap planes, and the same
+// epilogue from stored m and n; always an iteration's launch (exits at entry once the state is
+// done). The five sums per block go to ctx->d_partials (*nparts blocks)
+int launch_pcg_fused(pb_grid* g, const Star& s, const PcgVecs& v, const PcgState* ps,
+                     const CgState* st, bool nullspace, int* nparts) {
+  ScopedTimer tm(g->ctx, "pipecg_pass");
+  const StencilPlanes gp = wrap_planes();
+  const PcgEpi ep{v, ps, st};
+  const Launch lc = Launch{&st->done}.sums(0, nparts);
+  if (nullspace)
+    return launch_any(g, s, PcgLoad<true>{v.w, ps, st}, gp, ep, lc);
+  return launch_any(g, s, PcgLoad<false>{v.w, ps, st}, gp, ep, lc);
+}
+
+int launch_pcg_update(pb_grid* g, const double* m, const double* n, const PcgVecs& v,
+                      const PcgState* ps, const CgState* st, int* nparts) {
+  ScopedTimer tm(g->ctx, "pipecg_update");
+  return launch_tiled(g, m, n, PcgEpi{v, ps, st}, &st->done, nparts);
 }
 
 }  // namespace pb

@@ -1,6 +1,6 @@
 // pb_ksp_stationary.cpp -- the host drivers of the stationary solves:
 // -ksp_type richardson, chebyshev (with its eigenvalue estimate) and preonly. Their kernels and
-// launchers are in pb_ksp_stationary.hip, the fused update passes in pb_stencil.hip; the
+// launchers and the fused update passes are in pb_ksp_stationary.hip; the
 // device-resident state, done flags, history and polling are CG's (pb_solver.cpp).
 #include <cmath>
 #include <cstdio>

@@ -4,11 +4,12 @@
 // -ksp_type chebyshev (KSPSolve_Chebyshev) shares all of Richardson's but the update's expression
 // from its second update on and the omega recurrence in the finalize.
 // The hot step of Richardson on the 7-point operator is one stencil-engine pass (RichLoad /
-// RichEpi, pb_stencil.hip; Chebyshev: ChebLoad / RichEpi); the kernels here are its unfused form,
-// the steps around operators without an engine (compact, assembled, split grids) and the scalar
+// RichEpi, at the end of this file; Chebyshev: ChebLoad / RichEpi); the other kernels are its
+// unfused form, the steps around operators without an engine (compact, assembled, split grids) and the scalar
 // logic; their host drivers are in pb_ksp_stationary.cpp. The device-resident state, done flag,
 // history and polling are CG's (CgState, pb_solver.cpp).
 #include "pb_cg_device.hpp"
+#include "pb_star7.hpp"
 
 namespace pb {
 
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(256) void rich_x_kernel(const double* __restrict__ 
   }
 }
 
-// Chebyshev's update i >= 1 (cheb_step, pb_device.hpp: ChebLoad in pb_stencil.hip calls the same)
+// Chebyshev's update i >= 1 (cheb_step, pb_device.hpp: ChebLoad below calls the same)
 __global__ __launch_bounds__(256) void cheb_x_kernel(const double* __restrict__ y,
                                                      const double* __restrict__ ym1,
                                                      const double* __restrict__ q,
@@ -353,6 +354,146 @@ int launch_pre_shift(pb_grid* g, double* x, double ntot) {
                      g->ctx->stream, x, g->nlocal, (const double*)g->ctx->d_scalars, ntot);
   PB_HIP(hipGetLastError());
   return PB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The fused update passes on the stencil engine (pb_star7.hpp)
+// ---------------------------------------------------------------------------------------------
+// Richardson (-ksp_type richardson, PETSc KSPSolve_Richardson) on the 7-point operator: the update
+// and the residual in one pass. The field is x_new = x + scale (dinv q + shift), formed on load
+// from two raw arrays (q = r with Jacobi / no PC, the stored z = M^-1 r otherwise; shift = -mean,
+// the null-space removal), every product and sum rounded (no FMA contraction: the build's
+// -ffp-contract=off; rich_step in pb_device.hpp is the one definition), so rich_x_kernel
+// (pb_ksp_stationary.hip) gives the same bits. The epilogue stores the centre value x_new and
+// r_new = b - A x_new (reference summation order) and, with SUMS (Jacobi / no PC), takes the sums
+// of t = dinv r_new - mean_old (t, t^2) behind the next iteration's norm and mean. x and (SUMS) r
+// go to other buffers than they are read from: neighbouring waves and blocks still read x_old and
+// q at this point's neighbours while this block stores. Reads x, q, b and writes x, r: 40 B/DoF,
+// pass B's pattern (two streams written, non-temporal), whose launch shape it takes.
+// STOREX = false with PlainLoad: the unfused form's second step, r = b - A x of a stored x, with
+// the same tiles, chunks and partial sums (tuning rich_fused = 0; bit-identical).
+struct RichLoad {
+  static constexpr int NR = 2;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ x;
+  const double* __restrict__ q;
+  const CgState* st;
+  double scale;
+  double dinv = 1.0, shift = 0.0;
+  __device__ __forceinline__ void prepare() {
+    dinv = st->dinv;
+    shift = -st->mu;
+  }
+  __device__ __forceinline__ const double* src(int a) const { return a == 0 ? x : q; }
+  __device__ __forceinline__ double value(const double* raw) const {
+    return rich_step<true>(raw[0], raw[1], dinv, shift, scale);
+  }
+};
+// Chebyshev (-ksp_type chebyshev, PETSc KSPSolve_Chebyshev), update i >= 1: the field is
+// y_new = omega ((y - ym1) + scale (dinv q + shift)) + ym1, formed on load from three raw arrays
+// (omega = the state's alpha, advanced by the finalize before this pass), every operation rounded
+// in cheb_step's order (pb_device.hpp), as in cheb_x_kernel (pb_ksp_stationary.hip). RichEpi
+// stores y_new and r_new = b - A y_new: reads y, ym1, q, b and writes y, r, 48 B/DoF. y_new goes
+// to a third buffer: neighbouring waves and blocks still read y and ym1 around this point.
+struct ChebLoad {
+  static constexpr int NR = 3;
+  static constexpr bool GHOST_RAW = false;
+  const double* __restrict__ y;
+  const double* __restrict__ ym1;
+  const double* __restrict__ q;
+  const CgState* st;
+  double scale;
+  double dinv = 1.0, shift = 0.0, omega = 0.0;
+  __device__ __forceinline__ void prepare() {
+    dinv = st->dinv;
+    shift = -st->mu;
+    omega = st->alpha;
+  }
+  __device__ __forceinline__ const double* src(int a) const {
+    return a == 0 ? y : (a == 1 ? ym1 : q);
+  }
+  __device__ __forceinline__ double value(const double* raw) const {
+    return cheb_step<true>(raw[0], raw[1], raw[2], dinv, shift, scale, omega);
+  }
+};
+template <bool STOREX, bool SUMS>
+struct RichEpi {
+  static constexpr int NS = SUMS ? 2 : 0, NE = 1;
+  static constexpr bool RAW = false;
+  static constexpr int WGCU = 1;
+  static constexpr bool CAP = true, WIDE8 = true;
+  static constexpr bool PREFETCH = true;
+  double* __restrict__ x_out;
+  double* __restrict__ r_out;
+  const double* __restrict__ b;
+  const CgState* st;
+  double dinv = 1.0, mu = 0.0;
+  __device__ __forceinline__ void prepare() {
+    if constexpr (SUMS) {
+      dinv = st->dinv;
+      mu = st->mu;
+    }
+  }
+  __device__ __forceinline__ const double* src(int) const { return b; }
+  template <int V>
+  __device__ __forceinline__ void put(RowIx idx, const double (&c)[V], const double (&w)[V],
+                                      double (&op)[1][V], double* acc, int nt) const {
+    double rv[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      rv[e] = op[0][e] - w[e];
+      if constexpr (SUMS) {
+        const double s = dinv * rv[e];
+        const double t = s - mu;
+        acc[0] += t;
+        acc[1] += t * t;
+      }
+    }
+    (void)acc;
+    store_row<V>(r_out, idx, rv, nt);
+    if constexpr (STOREX) store_row<V>(x_out, idx, c, nt);
+  }
+};
+
+// Richardson's update + residual pass (RichLoad / RichEpi), whole grid, wrap planes or ghosts of
+// x as gp says. q != nullptr: fused, x_out = x + scale (dinv q - mean), r_out = b - A x_out;
+// q == nullptr: r_out = b - A x of the stored x (the unfused form and the nonzero-guess setup).
+// sums: the two sums of dinv r_out - mean per block into ctx->d_partials (*nparts blocks).
+// skip = false: the setup's launch (the state's done flag is not valid yet)
+int launch_rich_update(pb_grid* g, const Star& s, const double* x, const double* q,
+                       const double* b, double* x_out, double* r_out, const StencilPlanes& gp,
+                       const CgState* st, double scale, bool sums, bool skip, int* nparts,
+                       int part_off) {
+  ScopedTimer tm(g->ctx, q ? "rich_update" : "rich_resid");
+  const int* sk = skip ? &st->done : nullptr;
+  *nparts = 0;
+  if (q) {
+    const RichLoad ld{x, q, st, scale};
+    if (sums)
+      return launch_any(g, s, ld, gp, RichEpi<true, true>{x_out, r_out, b, st},
+                        Launch{sk}.sums(part_off, nparts));
+    return launch_any(g, s, ld, gp, RichEpi<true, false>{x_out, r_out, b, st}, Launch{sk});
+  }
+  if (sums)
+    return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, true>{nullptr, r_out, b, st},
+                      Launch{sk}.sums(part_off, nparts));
+  return launch_any(g, s, PlainLoad{x}, gp, RichEpi<false, false>{nullptr, r_out, b, st},
+                    Launch{sk});
+}
+
+// Chebyshev's update + residual pass for updates i >= 1 (ChebLoad / RichEpi), whole grid, wrap
+// planes; always an iteration's launch (exits at entry once the state is done)
+int launch_cheb_update(pb_grid* g, const Star& s, const double* y, const double* ym1,
+                       const double* q, const double* b, double* y_out, double* r_out,
+                       const StencilPlanes& gp, const CgState* st, double scale, bool sums,
+                       int* nparts, int part_off) {
+  ScopedTimer tm(g->ctx, "cheb_update");
+  *nparts = 0;
+  const ChebLoad ld{y, ym1, q, st, scale};
+  if (sums)
+    return launch_any(g, s, ld, gp, RichEpi<true, true>{y_out, r_out, b, st},
+                      Launch{&st->done}.sums(part_off, nparts));
+  return launch_any(g, s, ld, gp, RichEpi<true, false>{y_out, r_out, b, st}, Launch{&st->done});
 }
 
 }  // namespace pb

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void mg_prolong_z_kernel(MgGeo F, const double
 // Jacobi-type level smoothers (-mg_levels_pc_type jacobi under richardson or chebyshev). One step:
 //   y_new = omega ((y - yp) + scale (dinv r)) + yp,  dinv = 1 / cc,
 // every operation rounded in the order of its one definition (cheb_step, poly_second_step,
-// poly_start_step in pb_device.hpp, which PolyLoad in pb_stencil.hip calls too), so the engine
+// poly_start_step in pb_device.hpp, which PolyLoad in pb_mg_engine.hip calls too), so the engine
 // pass, the pair kernel and the vector kernel give the same bits. N = 3: y, yp, r; N = 2: y, r
 // (yp = 0 or Richardson); N = 1: the zero start, from b alone.
 // ---------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 // one rank or N (two-deep z ghosts exchanged per pass):
 // both half-sweeps of a post-smoothing in one pass, and the zero-start pre-smoothing fused with
 // the residual. Same per-point arithmetic as the half-sweep / residual kernels (SorHalf, ResidEpi
-// in pb_stencil.hip, restated in oracle/pb_oracle.c pbo_mg_apply), hence bit-identical results.
+// in pb_mg_engine.hip, restated in oracle/pb_oracle.c pbo_mg_apply), hence bit-identical results.
 #include <algorithm>
 #include <type_traits>
 
