@@ -3,8 +3,8 @@
 // device-resident state. Loaders and epilogues of pass A and pass B (with the p store in either,
 // the deferred x update, the finalize stages folded into their prologues), of the
 // single-reduction iteration's passes P and S and of the setup from a nonzero guess; the init,
-// boundary-plane, finalize and flush kernels; and every launch_cg_* / cg_finalize_* the host
-// driver (pb_solver.cpp) calls. The scalar logic itself is pb_cg_device.hpp's.
+// boundary-plane, finalize and flush kernels; and every launch_cg_* / cg_finalize_* / fold_* the
+// solver's host code (pb_ksp_cg.cpp) calls. The scalar logic itself is pb_cg_device.hpp's.
 #include "pb_star7.hpp"
 
 namespace pb {
@@ -408,9 +408,12 @@ __global__ __launch_bounds__(256) void cg_finalize_kernel(const double* __restri
   else st->delta = S[4];  // 3: the single-reduction setup's delta = z0'A z0
 }
 
-static int cg_reduce_update(pb_ctx* ctx, int stage, int nparts, int width, CgState* st,
-                            double* hist, int* h_done, int64_t host_iter,
-                            const double* parts = nullptr, const RrParts& rr = RrParts{}) {
+static int cg_reduce_update(pb_ctx* ctx, int stage, int nparts, int width, const KspLog& lg,
+                            int64_t host_iter, const double* parts = nullptr,
+                            const RrParts& rr = RrParts{}) {
+  CgState* st = lg.st;
+  double* hist = lg.hist;
+  int* h_done = lg.h_done;
   double* sums = ctx->d_scalars;
   if (!parts) parts = ctx->d_partials;
   ScopedTimer tm(ctx, "cg_finalize");  // (with its allreduce on several ranks)
@@ -441,15 +444,15 @@ static int elementwise_blocks(pb_ctx* ctx, int64_t n) {
   return (int)b;
 }
 
-int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, CgState* st,
-                   double dinv, double* hist, int* h_done) {
+int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, double dinv,
+                   const KspLog& lg) {
   pb_ctx* ctx = g->ctx;
   ScopedTimer tm(ctx, "cg_init");
   const int nb = elementwise_blocks(ctx, g->nlocal);
   hipLaunchKernelGGL(cg_init_kernel, dim3(nb), dim3(256), 0, ctx->stream, b, x, r, p, g->nlocal,
                      dinv, ctx->d_partials);
   PB_HIP(hipGetLastError());
-  return cg_reduce_update(ctx, 0, nb, 4, st, hist, h_done, -1);
+  return cg_reduce_update(ctx, 0, nb, 4, lg, -1);
 }
 
 // Setup from a nonzero initial guess: the fused pass (GuessInit) over the planes of `mode`; its
@@ -523,7 +526,10 @@ __global__ __launch_bounds__(256) void cg_guess_finalize_kernel(const double* __
 }
 
 int cg_finalize_guess(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
-                      CgState* st, double* hist, int* h_done, const RrParts& rr) {
+                      const KspLog& lg, const RrParts& rr) {
+  CgState* st = lg.st;
+  double* hist = lg.hist;
+  int* h_done = lg.h_done;
   double* sums = ctx->d_scalars;
   if (rr.parts && ((int64_t)nparts * width > ctx->partials_cap / 2 || width != 4))
     return set_error(PB_ERR_UNSUPPORTED, "unpreconditioned norm: partial sums do not fit");
@@ -568,54 +574,50 @@ int launch_cg_boundary(pb_grid* g, const double* r, const double* p_old, CgState
   return launch_cg_boundary(g, r, p_old, st, Fold{});
 }
 
-int launch_cg_pass_a(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                     double* p_new, const StencilPlanes& gp, CgState* st, int mode, int part_off,
-                     int* nblocks, bool store) {
+int launch_cg_pass_a(pb_grid* g, const Star& s, const CgPassA& a) {
   ScopedTimer tm(g->ctx,
-                 timer_name(mode, "cg_pass_a", "cg_pass_a_interior", "cg_pass_a_boundary"));
-  const CombineLoad ld{r, p_old, st, 0.0, 0.0, 0.0};
-  const Launch lc = Launch{&st->done, mode}.sums(part_off, nblocks);
-  if (!store) return launch_any(g, s, ld, gp, PassAT<false>{p_new}, lc);
-  return launch_any(g, s, ld, gp, PassA{p_new}, lc);
+                 timer_name(a.mode, "cg_pass_a", "cg_pass_a_interior", "cg_pass_a_boundary"));
+  // with a fold the prologue leaves the state (and the done flag) in registers
+  CgState* st = a.fold.stage ? nullptr : a.st;
+  const CombineLoad ld{a.r, a.p_old, st, 0.0, 0.0, 0.0};
+  Launch lc = Launch{st ? &st->done : nullptr, a.mode}.sums(a.part_off, a.nblocks);
+  lc.fold = a.fold;
+  if (!a.store) return launch_any(g, s, ld, a.gp, PassAT<false>{a.p_new}, lc);
+  return launch_any(g, s, ld, a.gp, PassA{a.p_new}, lc);
 }
 
-// Folded iteration (one rank, Jacobi): partial sums of pass A at block 0, of pass B at
-// fold_parts_b_off(); state slots st2[0] (read by pass B, written by pass A) and st2[1].
+// Folded iteration: partial sums of pass A at block 0, of pass B at fold_parts_b_off(); state
+// slots st2[0] (read by pass B, written by pass A) and st2[1].
 static int64_t fold_parts_b_off(const pb_ctx* ctx) { return ctx->partials_cap / 8; }
 
-int launch_cg_pass_a_folded(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                            double* p_new, const StencilPlanes& gp, CgState* st2, int nparts_b,
-                            double* hist, int* h_done, int64_t host_iter, int* nblocks,
-                            bool store) {
-  ScopedTimer tm(g->ctx, "cg_pass_a");
-  pb_ctx* ctx = g->ctx;
+static Fold fold_of(int stage, const double* parts, int nparts, int width, const CgState* in,
+                    CgState* out, const KspLog& lg, int64_t host_iter) {
   Fold f;
-  f.stage = 2;
-  f.nparts = nparts_b;
-  f.width = 4;
-  f.parts = ctx->d_partials + fold_parts_b_off(ctx) * 4;
-  f.in = st2 + 1;
-  f.out = st2;
-  f.hist = hist;
-  f.h_done = h_done;
-  f.host_iter = host_iter - 1;  // stage 2 of the previous iteration
-  const CombineLoad ld{r, p_old, nullptr, 0.0, 0.0, 0.0};
-  Launch lc = Launch{}.sums(0, nblocks);
-  lc.fold = f;
-  if (!store) return launch_any(g, s, ld, gp, PassAT<false>{p_new}, lc);
-  return launch_any(g, s, ld, gp, PassA{p_new}, lc);
+  f.stage = stage;
+  f.nparts = nparts;
+  f.width = width;
+  f.parts = parts;
+  f.in = in;
+  f.out = out;
+  f.hist = lg.hist;
+  f.h_done = lg.h_done;
+  f.host_iter = host_iter;
+  return f;
 }
-
-int launch_cg_pass_a_fold(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                          double* p_new, const StencilPlanes& gp, const Fold& fold, int mode,
-                          int part_off, int* nblocks, bool store) {
-  ScopedTimer tm(g->ctx,
-                 timer_name(mode, "cg_pass_a", "cg_pass_a_interior", "cg_pass_a_boundary"));
-  const CombineLoad ld{r, p_old, nullptr, 0.0, 0.0, 0.0};
-  Launch lc = Launch{nullptr, mode}.sums(part_off, nblocks);
-  lc.fold = fold;
-  if (!store) return launch_any(g, s, ld, gp, PassAT<false>{p_new}, lc);
-  return launch_any(g, s, ld, gp, PassA{p_new}, lc);
+Fold fold_stage2_allreduced(const pb_ctx* ctx, int width, const KspLog& lg, int64_t host_iter) {
+  return fold_of(2, ctx->d_scalars, 1, width, lg.st + 1, lg.st, lg, host_iter);
+}
+Fold fold_stage2_pass_b(const pb_ctx* ctx, int nparts_b, const KspLog& lg, int64_t host_iter) {
+  return fold_of(2, ctx->d_partials + fold_parts_b_off(ctx) * 4, nparts_b, 4, lg.st + 1, lg.st, lg,
+                 host_iter);
+}
+Fold fold_stage1_pass_a(const pb_ctx* ctx, int nparts_a, bool allreduced, CgState* st2) {
+  return fold_of(1, allreduced ? ctx->d_scalars : ctx->d_partials, nparts_a, 1, st2, st2 + 1,
+                 KspLog{nullptr, nullptr, nullptr}, 0);
+}
+Fold fold_sr_top(bool sums, const double* parts, int nparts_s, const CgState* in, CgState* out,
+                 const KspLog& lg, int64_t host_iter) {
+  return fold_of(sums ? 3 : 4, parts, nparts_s, 5, in, out, lg, host_iter);
 }
 
 // split grids, folded iteration: reduce a pass's partials and allreduce them into d_scalars, where
@@ -635,27 +637,25 @@ int cg_reduce_allreduce(pb_ctx* ctx, const double* parts, int nparts, int width)
 }
 
 // the residual-sum stage (2) on st in place from sums already allreduced into d_scalars
-int cg_stage2_from_sums(pb_ctx* ctx, int width, CgState* st, double* hist, int* h_done,
-                        int64_t host_iter) {
+int cg_stage2_from_sums(pb_ctx* ctx, int width, const KspLog& lg, int64_t host_iter) {
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
-                     (const double*)nullptr, 0, width, ctx->d_scalars, 2, 2, st, hist, h_done,
-                     host_iter, RrParts{});
+                     (const double*)nullptr, 0, width, ctx->d_scalars, 2, 2, lg.st, lg.hist,
+                     lg.h_done, host_iter, RrParts{});
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
-                     const RrParts& rr) {
-  return cg_reduce_update(ctx, 0, nparts, 4, st, hist, h_done, -1, nullptr, rr);
+int cg_finalize_init(pb_ctx* ctx, int nparts, const KspLog& lg, const RrParts& rr) {
+  return cg_reduce_update(ctx, 0, nparts, 4, lg, -1, nullptr, rr);
 }
 
 int cg_finalize_pass_a(pb_ctx* ctx, int nparts, CgState* st) {
-  return cg_reduce_update(ctx, 1, nparts, 1, st, nullptr, nullptr, 0);
+  return cg_reduce_update(ctx, 1, nparts, 1, KspLog{st, nullptr, nullptr}, 0);
 }
 
-int cg_finalize_stage2(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
-                       int64_t host_iter, const RrParts& rr) {
-  return cg_reduce_update(ctx, 2, nparts, 4, st, hist, h_done, host_iter, nullptr, rr);
+int cg_finalize_stage2(pb_ctx* ctx, int nparts, const KspLog& lg, int64_t host_iter,
+                       const RrParts& rr) {
+  return cg_reduce_update(ctx, 2, nparts, 4, lg, host_iter, nullptr, rr);
 }
 
 // pass B variants by the x-update position; fold.stage = 1: stage 1 in the prologue (partials
@@ -663,95 +663,50 @@ int cg_finalize_stage2(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* 
 // ps.r_out != nullptr (PB_CG_PSTORE_B): pass B re-forms p = CombineLoad(ps.zsrc, p_old) on load,
 // stores it to p, reads r and writes the new residual to ps.r_out.
 template <int XU, bool PST>
-static int pass_b_one(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
-                      double* x, double* r, const StencilPlanes& gp, CgState* st, const Fold& f,
-                      const PStore& ps, int* nparts, int part_off = 0) {
-  const int* skip = f.stage ? nullptr : &st->done;
-  const int off = f.stage ? (int)fold_parts_b_off(g->ctx) : part_off;
-  Launch lc = Launch{skip}.sums(off, nparts);
+static int pass_b_one(pb_grid* g, const Star& s, const CgPassB& b, const char* timer) {
+  ScopedTimer tm(g->ctx, timer);
+  CgState* st = b.fold.stage ? nullptr : b.st;
+  // rr: the sums go to the second region, where the PC's sums do not overwrite them
+  const int off = b.fold.stage ? (int)fold_parts_b_off(g->ctx)
+                               : (b.rr ? rr_part_off(g->ctx, 4) : 0);
+  Launch lc = Launch{st ? &st->done : nullptr}.sums(off, b.nparts);
   lc.rev = 1;  // (pass A marched upwards)
-  lc.fold = f;
-  PassB<XU, PST> ep{x, r, p_prev[0], XU == 3 ? p_prev[1] : nullptr, XU == 3 ? p_prev[2] : nullptr,
-                    st, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  lc.fold = b.fold;
+  PassB<XU, PST> ep{b.x, b.r, b.p_prev[0], XU == 3 ? b.p_prev[1] : nullptr,
+                    XU == 3 ? b.p_prev[2] : nullptr, st, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if constexpr (PST) {
-    ep.r_out = ps.r_out;
-    ep.p_out = const_cast<double*>(p);
-    CombineLoad ld{ps.zsrc, p_prev[0], st, 0.0, 0.0, 0.0};
+    ep.r_out = b.ps.r_out;
+    ep.p_out = const_cast<double*>(b.p);
+    CombineLoad ld{b.ps.zsrc, b.p_prev[0], st, 0.0, 0.0, 0.0};
     ld.after1 = 1;
-    return launch_any(g, s, ld, gp, ep, lc);
+    return launch_any(g, s, ld, b.gp, ep, lc);
   } else {
-    return launch_any(g, s, PlainLoad{p}, gp, ep, lc);
+    return launch_any(g, s, PlainLoad{b.p}, b.gp, ep, lc);
   }
 }
 
 template <bool PST>
-static int pass_b_pick(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
-                       double* x, double* r, const StencilPlanes& gp, CgState* st,
-                       int64_t host_iter, int defer, const Fold& f, const PStore& ps, int* nparts,
-                       int part_off) {
-  if (defer == 0) {
-    ScopedTimer tm(g->ctx, "cg_pass_b");
-    return pass_b_one<2, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
-  }
-  if (host_iter % defer != defer - 1) {
-    ScopedTimer tm(g->ctx, "cg_pass_b_even");
-    return pass_b_one<0, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
-  }
-  if (defer == 2) {
-    ScopedTimer tm(g->ctx, "cg_pass_b_odd");
-    return pass_b_one<1, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
-  }
-  ScopedTimer tm(g->ctx, "cg_pass_b_x4");
-  return pass_b_one<3, PST>(g, s, p, p_prev, x, r, gp, st, f, ps, nparts, part_off);
+static int pass_b_pick(pb_grid* g, const Star& s, const CgPassB& b) {
+  if (b.defer == 0) return pass_b_one<2, PST>(g, s, b, "cg_pass_b");
+  if (b.host_iter % b.defer != b.defer - 1) return pass_b_one<0, PST>(g, s, b, "cg_pass_b_even");
+  if (b.defer == 2) return pass_b_one<1, PST>(g, s, b, "cg_pass_b_odd");
+  return pass_b_one<3, PST>(g, s, b, "cg_pass_b_x4");
 }
 
-static int pass_b_launch(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
-                         double* x, double* r, const StencilPlanes& gp, CgState* st,
-                         int64_t host_iter, int defer, const Fold& f, const PStore& ps,
-                         int* nparts, int part_off = 0) {
-  if (ps.r_out)
-    return pass_b_pick<true>(g, s, p, p_prev, x, r, gp, st, host_iter, defer, f, ps, nparts,
-                             part_off);
-  return pass_b_pick<false>(g, s, p, p_prev, x, r, gp, st, host_iter, defer, f, ps, nparts,
-                            part_off);
-}
-
-int launch_cg_pass_b(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
-                     double* x, double* r, const StencilPlanes& gp, CgState* st, double* hist,
-                     int* h_done, int64_t host_iter, int defer, bool finalize, const PStore& ps,
-                     RrParts* rr) {
-  int nparts = 0;
-  // rr (unpreconditioned norm, stored-z PC): the four sums of t = r - mu this pass takes anyway
-  // go to the second region, where the PC's sums do not overwrite them (sum r^2 = t.r + mu r)
-  const int off = rr ? rr_part_off(g->ctx, 4) : 0;
-  PB_TRY(pass_b_launch(g, s, p, p_prev, x, r, gp, st, host_iter, defer, Fold{}, ps, &nparts, off));
-  if (rr) *rr = RrParts{rr_region(g->ctx), nparts, 4};
-  if (!finalize) return PB_OK;  // preconditioned path: the sums come from z = M^-1 r later
-  return cg_reduce_update(g->ctx, 2, nparts, 4, st, hist, h_done, host_iter);
-}
-
-int launch_cg_pass_b_folded(pb_grid* g, const Star& s, const double* p,
-                            const double* const* p_prev, double* x, double* r,
-                            const StencilPlanes& gp, CgState* st2, int nparts_a, int64_t host_iter,
-                            int defer, int* nparts_b, const PStore& ps, const double* parts_a) {
-  Fold f;
-  f.stage = 1;
-  f.nparts = nparts_a;
-  f.width = 1;
-  f.parts = parts_a ? parts_a : g->ctx->d_partials;
-  f.in = st2;
-  f.out = st2 + 1;
-  return pass_b_launch(g, s, p, p_prev, x, r, gp, nullptr, host_iter, defer, f, ps, nparts_b);
+int launch_cg_pass_b(pb_grid* g, const Star& s, const CgPassB& b) {
+  PB_TRY(b.ps.r_out ? pass_b_pick<true>(g, s, b) : pass_b_pick<false>(g, s, b));
+  if (b.rr) *b.rr = RrParts{rr_region(g->ctx), *b.nparts, 4};
+  return PB_OK;
 }
 
 // after the last folded iteration of a pb_ksp_iterate call: its stage 2 (in place on st2[1]),
 // then st2[0] = st2[1], so the unfolded entry points find the complete state in slot 0
-int cg_fold_tail(pb_ctx* ctx, int nparts_b, CgState* st2, double* hist, int* h_done,
-                 int64_t host_iter) {
+int cg_fold_tail(pb_ctx* ctx, int nparts_b, const KspLog& lg, int64_t host_iter) {
+  CgState* st2 = lg.st;
   // split grids: pass B's sums are already reduced and allreduced into d_scalars (mode 2 only)
   hipLaunchKernelGGL(cg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream,
                      ctx->d_partials + fold_parts_b_off(ctx) * 4, nparts_b, 4, ctx->d_scalars,
-                     ctx->split ? 2 : 3, 2, st2 + 1, hist, h_done, host_iter, RrParts{});
+                     ctx->split ? 2 : 3, 2, st2 + 1, lg.hist, lg.h_done, host_iter, RrParts{});
   PB_HIP(hipGetLastError());
   PB_HIP(hipMemcpyAsync(st2, st2 + 1, sizeof(CgState), hipMemcpyDeviceToDevice, ctx->stream));
   return PB_OK;
@@ -780,17 +735,7 @@ static int sr_pass_p_one(pb_grid* g, const Star& s, const double* r, const doubl
 
 int launch_cg_sr_pass_p(pb_grid* g, const Star& s, const double* r, const double* const* p_prev,
                         double* p_new, double* x, double* r_out, const StencilPlanes& gp,
-                        const SrFold& sf, int mode, int64_t host_iter, int defer) {
-  Fold f;
-  f.stage = sf.fold_sums ? 3 : 4;
-  f.nparts = sf.nparts_s;
-  f.width = 5;
-  f.parts = sf.parts ? sf.parts : g->ctx->d_partials;
-  f.in = sf.in;
-  f.out = sf.out;
-  f.hist = sf.hist;
-  f.h_done = sf.h_done;
-  f.host_iter = host_iter - 1;  // the residual-sum stage of the previous iteration
+                        const Fold& f, int mode, int64_t host_iter, int defer) {
   if (defer == 4 && host_iter % 4 == 3) {
     ScopedTimer tm(g->ctx, timer_name(mode, "cg_sr_p_x4", "cg_sr_p_x4_interior", "cg_sr_p_x4_boundary"));
     return sr_pass_p_one<3>(g, s, r, p_prev, p_new, x, r_out, gp, f, mode);
@@ -822,10 +767,9 @@ int launch_cg_sr_pass_s(pb_grid* g, const Star& s, const double* r, const Stenci
   return launch_any(g, s, ZLoad{r, st}, gp, SrSums{}, lc);
 }
 
-int cg_sr_finalize(pb_ctx* ctx, const double* parts, int nparts, CgState* st, double* hist,
-                   int* h_done, int64_t host_iter, bool stage_delta0) {
-  return cg_reduce_update(ctx, stage_delta0 ? 3 : 2, nparts, 5, st, hist, h_done, host_iter,
-                          parts);
+int cg_sr_finalize(pb_ctx* ctx, const double* parts, int nparts, const KspLog& lg,
+                   int64_t host_iter, bool stage_delta0) {
+  return cg_reduce_update(ctx, stage_delta0 ? 3 : 2, nparts, 5, lg, host_iter, parts);
 }
 
 // x += alpha * p (the pending half of the deferred solution update)

@@ -401,9 +401,8 @@ bool cg_sr1_supported(const pb_grid* g) {
          tune("cg_sr_fused", 1) != 0;
 }
 
-int launch_cg_sr1(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                  double* p_new, double* r_out, const SrFold& sf, const double* parts_in,
-                  double* parts_out, int64_t host_iter, int* nblocks) {
+int launch_cg_sr1(pb_grid* g, const Star& s, const double* r, const double* p_old, double* p_new,
+                  double* r_out, const Fold& f, double* parts_out, int* nblocks) {
 #ifndef PB_SR_TY
 #define PB_SR_TY 2
 #endif
@@ -435,16 +434,6 @@ int launch_cg_sr1(pb_grid* g, const Star& s, const double* r, const double* p_ol
   const int64_t nb = (work + geo.W - 1) / geo.W;
   if (nb * 5 > ctx->partials_cap / 2)
     return set_error(PB_ERR_UNSUPPORTED, "single-reduction pass of %lld blocks", (long long)nb);
-  Fold f;
-  f.stage = sf.fold_sums ? 3 : 4;
-  f.nparts = sf.nparts_s;
-  f.width = 5;
-  f.parts = parts_in;
-  f.in = sf.in;
-  f.out = sf.out;
-  f.hist = sf.hist;
-  f.h_done = sf.h_done;
-  f.host_iter = host_iter - 1;
   if (dd)
     hipLaunchKernelGGL((cg_sr1_kernel<NW, TY, V, true>), dim3((unsigned)nb), dim3(64 * NW), 0,
                        ctx->stream, geo, s.cx, s.cy, s.cz, s.cc, r, p_old, p_new, r_out, parts_out,

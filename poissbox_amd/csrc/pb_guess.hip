@@ -1,5 +1,5 @@
 // pb_guess.hip -- multi-vector kernels (PETSc VecMDot / VecMAXPY analogues) behind pb_vec_mdot,
-// pb_vec_maxpy and the projected initial guess (-ksp_guess_type fischer, pb_solver.cpp).
+// pb_vec_maxpy and the projected initial guess (-ksp_guess_type fischer, pb_ksp_guess.cpp).
 // One pass each: every stream is read once with 16-byte loads, two loads per stream in flight per
 // thread; grid-stride with a block cap; an odd length ends in a scalar tail. Plain loads and
 // stores: non-temporal stores measured no faster (profiles/guess_fischer/README.md). The sums are

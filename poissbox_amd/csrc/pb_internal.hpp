@@ -219,11 +219,10 @@ struct ScopedTimer {
 int halo_exchange(pb_grid* g, const double* lo, const double* hi);
 // Split form: begin (RCCL on the context's comm stream after an event on the compute stream;
 // host transport: synchronous), end (compute stream waits for the exchange).
-int halo_begin(pb_grid* g, const double* lo, const double* hi);
-// halo_begin with the boundary planes produced on the comm stream first (RCCL split grids): pre
-// enqueues their kernel on the given stream after the context stream's work so far
-int halo_begin_after(pb_grid* g, const double* lo, const double* hi,
-                     const std::function<int(hipStream_t)>& pre);
+// pre (optional): the boundary planes are produced on the comm stream first (RCCL split grids) --
+// pre enqueues their kernel on the given stream after the context stream's work so far
+int halo_begin(pb_grid* g, const double* lo, const double* hi,
+               const std::function<int(hipStream_t)>& pre = {});
 // np-plane exchange into explicit buffers: send the np planes at `lo` (first owned) to rank-1
 // and at `hi` (last owned) to rank+1; rlo receives the np planes below the slab (from rank-1),
 // rhi the np planes above it (from rank+1). Stream ordered; one rank: periodic copies.
@@ -283,6 +282,35 @@ enum { PLANES_ALL = 0, PLANES_INTERIOR = 1, PLANES_BOUNDARY = 2 };
 __attribute__((visibility("hidden"))) const char* timer_name(int mode, const char* all,
                                                              const char* interior,
                                                              const char* boundary);
+// An engine pass with its halo exchange: launch(mode, gp, part_off, &nblocks) runs the pass over
+// the planes of `mode`, its partial sums from block part_off on.
+//   one rank: one launch over all planes with the caller's planes `one` (wrap_planes(), or ghost
+//     pointers to the wrap planes: the two select different engine geometry);
+//   fewer than three planes per rank: the exchange of the planes lo / hi, then one launch;
+//   else the exchange under the interior planes and the two boundary planes behind it, their
+//     partials behind the interior launch's, the whole under the timer `timer`.
+// *nblocks = the blocks launched (partial sums written), if the pass reports them
+template <class LaunchFn>
+int halo_overlap(pb_grid* g, const double* lo, const double* hi, const StencilPlanes& one,
+                 const char* timer, int part_off, int* nblocks, LaunchFn&& launch) {
+  pb_ctx* ctx = g->ctx;
+  if (!ctx->split) return launch(PLANES_ALL, one, part_off, nblocks);
+  StencilPlanes gp;
+  gp.ghost_lo = g->ghost_lo;
+  gp.ghost_hi = g->ghost_hi;
+  if (g->nzl < 3) {
+    PB_TRY(halo_exchange(g, lo, hi));
+    return launch(PLANES_ALL, gp, part_off, nblocks);
+  }
+  int nb1 = 0, nb2 = 0;
+  ScopedTimer tm(ctx, timer);  // both launches and the wait
+  PB_TRY(halo_begin(g, lo, hi));
+  PB_TRY(launch(PLANES_INTERIOR, gp, part_off, &nb1));
+  PB_TRY(halo_end(g));
+  PB_TRY(launch(PLANES_BOUNDARY, gp, part_off + nb1, &nb2));
+  *nblocks = nb1 + nb2;
+  return PB_OK;
+}
 int launch_star7_apply(pb_grid* g, const Star& s, const double* x, double* y,
                        const StencilPlanes& gp, int mode);
 // assembled P (pb_assembled.hip): re-sum the seam and slab-boundary rows of y = P x in PETSc AIJ
@@ -357,8 +385,15 @@ struct RrParts {
 inline double* rr_region(const pb_ctx* ctx) { return ctx->d_partials + ctx->partials_cap / 2; }
 // (in blocks of ns sums, as launch_any's part_off)
 inline int rr_part_off(const pb_ctx* ctx, int ns) { return (int)(ctx->partials_cap / 2 / ns); }
-int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, CgState* st,
-                   double dinv, double* hist, int* h_done);
+// what every solver's scalar stage writes: a state slot, the residual history and the host-mapped
+// done flags (pb_ksp::log())
+struct KspLog {
+  CgState* st;
+  double* hist;
+  int* h_done;
+};
+int launch_cg_init(pb_grid* g, const double* b, double* x, double* r, double* p, double dinv,
+                   const KspLog& lg);
 // Setup from a nonzero initial guess (-ksp_initial_guess_nonzero; x0 is never written):
 //  - fused operator, Jacobi / no PC: one engine pass (pb_cg_passes.hip GuessInit) reads x0 and b,
 //    stores r = b - A x0 and p = 0, and takes six sums per block (the setup's four of dinv r,
@@ -376,7 +411,7 @@ int launch_cg_guess_init(pb_grid* g, const Star& s, const double* x0, const doub
 int launch_cg_guess_resid(pb_grid* g, const double* b, const double* w, double* r, double* p,
                           double dinv, int* nparts, RrParts* rr = nullptr);
 int cg_finalize_guess(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
-                      CgState* st, double* hist, int* h_done, const RrParts& rr = RrParts{});
+                      const KspLog& lg, const RrParts& rr = RrParts{});
 struct Fold {
   // 0: no fold; 1: stage 1 (pass B); 2: stage 2 (pass A); single-reduction pass P: 3: the
   // residual-sum stage of the previous iteration, then the top of this one; 4: the top only
@@ -394,20 +429,44 @@ struct Fold {
 int launch_cg_boundary(pb_grid* g, const double* r, const double* p_old, CgState* st,
                        const Fold& fold, hipStream_t stream = nullptr);
 int launch_cg_boundary(pb_grid* g, const double* r, const double* p_old, CgState* st);
-// pass A launch (mode: PLANES_*) whose prologue runs fold (stage 2, split grids)
-int launch_cg_pass_a_fold(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                          double* p_new, const StencilPlanes& gp, const Fold& fold, int mode,
-                          int part_off, int* nblocks, bool store);
+// The folds of the KSPSolve_CG iteration (pb_cg_passes.hip, beside the partial-region layout).
+// lg = the KSP's log on slot 0; the folded iteration keeps its state in the two slots lg.st[0..1]:
+// stage 2 of iteration host_iter (the one before the launch's) runs slot 1 -> slot 0, from
+//   fold_stage2_allreduced: one allreduced partial of `width` sums in ctx->d_scalars (split grids);
+//   fold_stage2_pass_b: the nparts_b blocks of pass B's partial region (one rank);
+// stage 1 runs slot 0 -> slot 1 from pass A's nparts_a blocks at block 0 (allreduced: from the one
+// partial in ctx->d_scalars instead)
+#pragma GCC visibility push(hidden)
+Fold fold_stage2_allreduced(const pb_ctx* ctx, int width, const KspLog& lg, int64_t host_iter);
+Fold fold_stage2_pass_b(const pb_ctx* ctx, int nparts_b, const KspLog& lg, int64_t host_iter);
+Fold fold_stage1_pass_a(const pb_ctx* ctx, int nparts_a, bool allreduced, CgState* st2);
+// the single-reduction pass P's prologue: sums = the residual-sum stage of iteration host_iter
+// (the one before the launch's) from pass S's nparts_s blocks (5 wide) at `parts` first (stage 3),
+// else the state in `in` is complete (stage 4); then the top of the iteration, in -> out
+Fold fold_sr_top(bool sums, const double* parts, int nparts_s, const CgState* in, CgState* out,
+                 const KspLog& lg, int64_t host_iter);
+#pragma GCC visibility pop
 // split grids, folded iteration: a pass's partials reduced and allreduced into ctx->d_scalars
 int cg_reduce_allreduce(pb_ctx* ctx, int nparts, int width, bool b_region);
 int cg_reduce_allreduce(pb_ctx* ctx, const double* parts, int nparts, int width);
-// stage 2 on st in place from the sums cg_reduce_allreduce left in ctx->d_scalars
-int cg_stage2_from_sums(pb_ctx* ctx, int width, CgState* st, double* hist, int* h_done,
-                        int64_t host_iter);
-// store = false: pass A only takes p.Ap; pass B forms and stores p (PB_CG_PSTORE_B, PStore)
-int launch_cg_pass_a(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                     double* p_new, const StencilPlanes& gp, CgState* st, int mode, int part_off,
-                     int* nblocks, bool store = true);
+// stage 2 on lg.st in place from the sums cg_reduce_allreduce left in ctx->d_scalars
+int cg_stage2_from_sums(pb_ctx* ctx, int width, const KspLog& lg, int64_t host_iter);
+// Pass A over the planes of `mode`: p_new = (dinv r - mu) + beta / betaold p_old combined on load,
+// the partial sums of p.Ap from block part_off on, *nblocks of them
+struct CgPassA {
+  const double* r = nullptr;  // the array combined: r (Jacobi / none) or the stored z
+  const double* p_old = nullptr;
+  double* p_new = nullptr;
+  StencilPlanes gp;
+  int mode = PLANES_ALL;
+  int part_off = 0;
+  int* nblocks = nullptr;
+  // false: pass A only takes p.Ap; pass B forms and stores p (PB_CG_PSTORE_B, PStore)
+  bool store = true;
+  CgState* st = nullptr;  // the state read (not with a fold: its prologue leaves the state)
+  Fold fold;              // stage 2 of the previous iteration in the prologue
+};
+int launch_cg_pass_a(pb_grid* g, const Star& s, const CgPassA& a);
 // pass B re-forming p (PB_CG_PSTORE_B): zsrc = the array pass A combined (r), r_out = the
 // residual's other buffer; r_out == nullptr: p is read as stored by pass A, r updated in place
 struct PStore {
@@ -415,64 +474,49 @@ struct PStore {
   double* r_out = nullptr;
 };
 int cg_finalize_pass_a(pb_ctx* ctx, int nparts, CgState* st);
-// p_prev[m] = p of iteration host_iter - 1 - m (m < 3; only the first defer-1 are read)
-int launch_cg_pass_b(pb_grid* g, const Star& s, const double* p, const double* const* p_prev,
-                     double* x, double* r, const StencilPlanes& gp, CgState* st, double* hist,
-                     int* h_done, int64_t host_iter, int defer, bool finalize = true,
-                     const PStore& ps = PStore{}, RrParts* rr = nullptr);
+// Pass B: w = A p, the x / r update by the position of host_iter in the deferral, the four residual
+// sums, *nparts blocks of them: at block 0 for cg_finalize_stage2, in pass B's partial region with
+// a fold, in the second region with rr (unpreconditioned norm with a stored-z PC: sum r^2 =
+// t.r + mu r from the sums of t = r - mu this pass takes anyway; the PC's sums do not reach them)
+struct CgPassB {
+  const double* p = nullptr;
+  const double* const* p_prev = nullptr;  // p of iterations host_iter - 1 - m, m < 3
+  double* x = nullptr;
+  double* r = nullptr;
+  StencilPlanes gp;
+  int64_t host_iter = 0;
+  int defer = 0;
+  PStore ps;
+  int* nparts = nullptr;
+  CgState* st = nullptr;  // the state read and updated (not with a fold)
+  Fold fold;              // stage 1 in the prologue
+  RrParts* rr = nullptr;
+};
+int launch_cg_pass_b(pb_grid* g, const Star& s, const CgPassB& b);
 int launch_cg_flush(pb_grid* g, double* x, const double* p, double alpha);
-// Folded single-rank Jacobi iteration (finalize in the passes' prologues, pb_cg_passes.hip): state
-// in two slots st2[0..1]; pass A of iteration host_iter >= 1 runs stage 2 of host_iter - 1
-// (st2[1] -> st2[0], history and done flag as finalize's), pass B stage 1 (st2[0] -> st2[1]);
-// cg_fold_tail completes the last iteration of a batch and leaves the state in st2[0].
-int launch_cg_pass_a_folded(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                            double* p_new, const StencilPlanes& gp, CgState* st2, int nparts_b,
-                            double* hist, int* h_done, int64_t host_iter, int* nblocks,
-                            bool store = true);
-int launch_cg_pass_b_folded(pb_grid* g, const Star& s, const double* p,
-                            const double* const* p_prev, double* x, double* r,
-                            const StencilPlanes& gp, CgState* st2, int nparts_a, int64_t host_iter,
-                            int defer, int* nparts_b, const PStore& ps = PStore{},
-                            const double* parts_a = nullptr);
-int cg_fold_tail(pb_ctx* ctx, int nparts_b, CgState* st2, double* hist, int* h_done,
-                 int64_t host_iter);
+// after the last folded iteration of a batch: its stage 2 in place on slot 1, then slot 0 = slot 1
+int cg_fold_tail(pb_ctx* ctx, int nparts_b, const KspLog& lg, int64_t host_iter);
 // Single-reduction CG (PETSc KSPSolve_CG_SingleReduction, -ksp_cg_single_reduction), two engine
 // passes per iteration and ONE reduction (pb_cg_passes.hip):
-//   pass P: prologue = [the previous iteration's residual-sum stage (folded, one rank)] + the top
-//     of the iteration (beta / betaold, p'w = delta - beta^2 dpiold / betaold^2, alpha); body:
-//     p = (dinv r - mu) + b p_old on load, w = A p, r_out = r - alpha w, store p and r_out, the
-//     deferred x update every defer-th iteration. Reads state slot `in`, writes slot `out`.
+//   pass P: prologue = fold_sr_top; body: p = (dinv r - mu) + b p_old on load, w = A p,
+//     r_out = r - alpha w, store p and r_out, the deferred x update every defer-th iteration.
 //   pass S: t = dinv r_out - mu on load, s = A t; per-block sums t, t^2, t.r, r, t.s (5 wide)
 //     into ctx->d_partials + part_off * 5.
-// fold_sums: 1 = the prologue first reduces pass S's partials (nparts_s blocks at offset 0) and
-// runs their stage (history / done flag of host_iter - 1); 0 = the state in `in` is complete.
-struct SrFold {
-  int fold_sums = 0;
-  int nparts_s = 0;
-  const double* parts = nullptr;  // the partials fold_sums reduces (5 wide)
-  const CgState* in = nullptr;
-  CgState* out = nullptr;
-  double* hist = nullptr;
-  int* h_done = nullptr;
-};
 int launch_cg_sr_pass_p(pb_grid* g, const Star& s, const double* r, const double* const* p_prev,
                         double* p_new, double* x, double* r_out, const StencilPlanes& gp,
-                        const SrFold& f, int mode, int64_t host_iter, int defer);
+                        const Fold& f, int mode, int64_t host_iter, int defer);
 int launch_cg_sr_pass_s(pb_grid* g, const Star& s, const double* r, const StencilPlanes& gp,
                         const CgState* st, int mode, int part_off, int part_end,
                         int* nblocks);
 // after pass S (unfolded): reduce its partials `parts` (+ allreduce on split grids) and run the
-// residual-sum stage on st in place (stage_delta0: the setup's delta = z0'A z0 only)
-int cg_sr_finalize(pb_ctx* ctx, const double* parts, int nparts, CgState* st, double* hist,
-                   int* h_done, int64_t host_iter, bool stage_delta0 = false);
+// residual-sum stage on lg.st in place (stage_delta0: the setup's delta = z0'A z0 only)
+int cg_sr_finalize(pb_ctx* ctx, const double* parts, int nparts, const KspLog& lg,
+                   int64_t host_iter, bool stage_delta0 = false);
 // The same iteration as ONE pass (pb_cg_sr.hip; one rank, even nx, tuning cg_sr_fused): p, r',
-// and all five sums; the prologue as pass P's (sf), partials into parts_out (*nblocks blocks)
+// and all five sums; the prologue as pass P's (f), partials into parts_out (*nblocks blocks)
 bool cg_sr1_supported(const pb_grid* g);
-// x != nullptr: the iteration also carries the depth-4 deferred x update (p_m2, p_m3 = p_{i-2},
-// p_{i-3}; p_{i-1} is p_old)
-int launch_cg_sr1(pb_grid* g, const Star& s, const double* r, const double* p_old,
-                  double* p_new, double* r_out, const SrFold& sf, const double* parts_in, double* parts_out, int64_t host_iter,
-                  int* nblocks);
+int launch_cg_sr1(pb_grid* g, const Star& s, const double* r, const double* p_old, double* p_new,
+                  double* r_out, const Fold& f, double* parts_out, int* nblocks);
 
 // ---- compact fast path + generic CG (pb_compact_fast.hip) ----
 int64_t compact_fast_work_len(const pb_grid* g);
@@ -599,8 +643,8 @@ int launch_cg_generic_p(pb_grid* g, const double* r, double* p, CgState* st, int
 int launch_cg_generic_dot(pb_grid* g, const double* p, const double* w, CgState* st, int* nparts);
 int launch_cg_generic_xr(pb_grid* g, const double* p, const double* w, double* x, double* r,
                          CgState* st, int* nparts);
-int cg_finalize_stage2(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
-                       int64_t host_iter, const RrParts& rr = RrParts{});
+int cg_finalize_stage2(pb_ctx* ctx, int nparts, const KspLog& lg, int64_t host_iter,
+                       const RrParts& rr = RrParts{});
 
 // ---- vector ops (pb_vecops.hip) ----
 int vec_fill(pb_ctx* ctx, double* d, int64_t n, double a);
@@ -651,8 +695,7 @@ int launch_cg_pc_xr(pb_grid* g, const double* p, const double* w, double* x, con
 int launch_cg_pc_sums(pb_grid* g, const double* z, const double* r, CgState* st, int* nparts);
 // sum r^2 per block into rr_region (the setup from a zero guess: r_0 = b)
 int launch_cg_rr(pb_grid* g, const double* r, RrParts* rr);
-int cg_finalize_init(pb_ctx* ctx, int nparts, CgState* st, double* hist, int* h_done,
-                     const RrParts& rr = RrParts{});
+int cg_finalize_init(pb_ctx* ctx, int nparts, const KspLog& lg, const RrParts& rr = RrParts{});
 
 // ---- stationary solves: -ksp_type richardson / preonly (pb_ksp_stationary.hip, and the engine
 // pass launch_rich_update in pb_ksp_stationary.hip) ----
@@ -683,8 +726,8 @@ int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst,
 // 1 / mu), st->alpha = omega_i = omegaprod rho_i -- CG's two fields, unused by these solves
 // rr (unpreconditioned norm with a stored-z PC): the two sums of t = r - mean the residual pass
 // left in the second partial region (RrParts width 2), behind ||r||
-int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
-                  double* hist, int* h_done, int64_t host_iter, double cheb_mu = 0.0,
+int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
+                  const KspLog& lg, int64_t host_iter, double cheb_mu = 0.0,
                   double cheb_omegaprod = 0.0, const RrParts& rr = RrParts{});
 // Chebyshev's update i >= 1 (pb_ksp_stationary.hip ChebLoad): y_out = omega ((y - ym1) + scale (dinv q -
 // mean)) + ym1 with omega = st->alpha, r_out = b - A y_out, one rank, wrap planes; sums as

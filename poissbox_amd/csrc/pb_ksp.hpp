@@ -1,6 +1,6 @@
-// pb_ksp.hpp -- struct pb_ksp and what the KSP's host files share: pb_solver.cpp (create / begin /
-// iterate / end, the CG enqueue paths), pb_ksp_stationary.cpp (richardson, chebyshev, preonly),
-// pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers),
+// pb_ksp.hpp -- struct pb_ksp and what the KSP's host files share: pb_solver.cpp (the driver: create
+// / begin / iterate / end / solve), pb_ksp_cg.cpp (cg), pb_ksp_stationary.cpp (richardson, chebyshev,
+// preonly), pb_ksp_guess.cpp (the projected initial guess), pb_options.cpp (defaults, checks, parsers),
 // pb_norm_type.cpp (-ksp_norm_type), pb_ksp_fgmres.cpp (fgmres), pb_ksp_pipecg.cpp (pipecg) and
 // pb_op.cpp (the operator).
 #pragma once
@@ -110,6 +110,8 @@ struct pb_ksp {
   Pipecg pcg;
   bool pipecg() const { return opts.ksp_type == PB_KSP_PIPECG; }
   double* pcg_wbuf(int i) const { return (i & 1) ? pcg.w2 : pb[1]; }
+  // the default solver (pb_ksp_cg.cpp): the split form of every type that is none of the above
+  bool cg() const { return !rich() && !fgmres() && !pipecg(); }
   pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
   pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
@@ -123,6 +125,15 @@ struct pb_ksp {
   int* h_done = nullptr;      // host-mapped, one flag per host iteration (+1)
   int* h_done_dev = nullptr;  // its device alias
   int64_t done_cap = 0;
+  // what the scalar stages write: state slot 0 (1: the folded iterations' second), history, flags
+  pb::KspLog log(int slot = 0) const { return pb::KspLog{d_st + slot, d_hist, h_done_dev}; }
+  // KSPConvergedDefault's reference norm from a nonzero guess: REF_INITIAL, REF_MIN or REF_RHS
+  // (pb_cg_device.hpp)
+  int ref_norm() const {
+    return opts.converged_use_initial_residual_norm
+               ? 1
+               : (opts.converged_use_min_initial_residual_norm ? 2 : 0);
+  }
   std::vector<hipEvent_t> ring;
   // solve state
   const pb_vec* b = nullptr;
@@ -132,6 +143,19 @@ struct pb_ksp {
   bool begun = false;
   int defer_x = 4;  // x updated every defer_x-th iteration (PB_CG_DEFER_X = 0, 2 or 4)
   int pslots() const { return defer_x == 4 ? 4 : 2; }
+  // the vectors of CG's iteration i (= host_iter) on the fused operator: p of iterations i - 1
+  // (p_old = p_prev[0]), i - 2, i - 3 (the depth-4 deferral reads all three at i % 4 == 3), the
+  // direction and the residual it writes
+  struct CgBufs {
+    const double* p_prev[3];
+    double *p_old, *p_new, *r, *r_out;
+  };
+  CgBufs cg_bufs() const {
+    const int64_t i = host_iter;
+    const int ns = pslots();
+    return CgBufs{{pb[i % ns], pb[(i + ns - 1) % ns], pb[(i + ns - 2) % ns]},
+                  pb[i % ns], pb[(i + 1) % ns], rbuf(i), rbuf(i + 1)};
+  }
   // single-reduction iteration (-ksp_cg_single_reduction on the fused operator, Jacobi / none):
   // the state alternates between the two slots d_st[0..1] within a pb_ksp_iterate batch (pass P
   // of the batch's n-th iteration reads slot n & 1 and writes the other); nparts = pass S's
@@ -172,11 +196,22 @@ struct OpApplySkip {
   ~OpApplySkip() { ctx->op_skip = nullptr; }
 };
 
-// ---- pb_solver.cpp ----
+// ---- pb_solver.cpp: the driver ----
 int ensure_done_cap(pb_ksp* k, int64_t need);
 // z = M^-1 r for the stored-z preconditioners; *np = residual-sum partial blocks written by the
 // PC itself (MG's last sweep), 0 if the caller must take the sums
 int pc_apply_dev(pb_ksp* k, const double* r, double* z, const int* skip, int* np);
+
+// ---- pb_ksp_cg.cpp: -ksp_type cg ----
+// pb_ksp_begin's setup (it uploads the state itself: st, the tolerances filled in, gets the form
+// of this solve's iteration first); iteration n of a pb_ksp_iterate batch (fold: the finalize
+// steps run in the passes' prologues); what completes a batch of n iterations (the folded last
+// iteration's residual-sum stage, the state back into slot 0); pb_ksp_end's share from the final
+// state st: the deferred part of the x update, x = 0 after a lazy start that never iterated
+int cg_begin(pb_ksp* k, const pb_vec* b, pb_vec* x, CgState& st);
+int enqueue_cg_iteration(pb_ksp* k, bool fold, int64_t n);
+int cg_batch_end(pb_ksp* k, bool fold, int64_t n);
+int cg_finish(pb_ksp* k, const CgState& st);
 
 // ---- pb_options.cpp: every range and compatibility rule of the option structs ----
 // Chebyshev's interval: finite, non-zero, of one sign, emax > emin (`what` names it in the error)
@@ -256,12 +291,11 @@ int launch_fg_fused(pb_grid* g, const Star& s, const double* wt, double* v, doub
 // the first test, restart / haptol into the state); mode 1: a restart (the recomputed ||r||
 // tested at the same iteration count, not logged). Both start a cycle: loc = 0, g_0 = ||r||,
 // scale = 1 / ||r||
-int launch_fg_start(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_done, int mode,
-                    int ref, int restart, double haptol, int64_t host_iter);
+int launch_fg_start(pb_ctx* ctx, const KspLog& lg, FgState* fs, int mode, int ref, int restart,
+                    double haptol, int64_t host_iter);
 // one Arnoldi step's scalar part: the column from the sums (passes = 2: dots + dots2), the
 // happy-breakdown check, the rotations, the estimate logged and tested, the done flag
-int launch_fg_step(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_done, int passes,
-                   int64_t host_iter);
+int launch_fg_step(pb_ctx* ctx, const KspLog& lg, FgState* fs, int passes, int64_t host_iter);
 // y = the triangular solve over the live columns; x = x + (((0 + y_0 z_0) + y_1 z_1) + ...) over
 // the live count read from the device. force = false: exit at entry when the state is done (a
 // restart enqueued ahead); true: pb_ksp_end's build of the cycle the solve ended in
@@ -309,8 +343,8 @@ int launch_pcg_sums(pb_ctx* ctx, const double* r, const double* u, const double*
 // tested (KSPConvergedDefault), the iteration limit, beta, alpha (the i = 0 branch from the
 // device's update count), the done flag. setup: pb_ksp_begin's (ref = REF_*, its = 0), else the
 // update count advances first
-int launch_pcg_finalize(pb_ctx* ctx, CgState* st, PcgState* ps, const double* parts, int nparts,
-                        double* hist, int* h_done, bool setup, int ref, int64_t host_iter);
+int launch_pcg_finalize(pb_ctx* ctx, const KspLog& lg, PcgState* ps, const double* parts,
+                        int nparts, bool setup, int ref, int64_t host_iter);
 // ---- pb_ksp_pipecg.hip: the update pass on the stencil engine (pb_star7.hpp) ----
 // The iteration on the 7-point operator with Jacobi / no PC (one rank, wrap planes; PcgLoad /
 // PcgEpi): m = dinv w + shift formed on load, n = A m, the eight updates and the five sums of the

@@ -116,16 +116,13 @@ int pb::fgmres_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
     PB_HIP(hipMemcpyAsync(w, b->d, vb, hipMemcpyDeviceToDevice, ctx->stream));
   } else {
     PB_TRY(check_ref_norm_opts(&k->opts));
-    ref = k->opts.converged_use_initial_residual_norm
-              ? REF_INITIAL
-              : (k->opts.converged_use_min_initial_residual_norm ? REF_MIN : REF_RHS);
+    ref = k->ref_norm();
     if (ref != REF_INITIAL && !k->norm_none()) PB_TRY(fg_norm2(ctx, b->d, n, &fs->bsq, false));
     PB_TRY(op_apply_raw(k->A, x->d, k->r));
     PB_TRY(launch_guess_diff(ctx, b->d, k->r, w, n));
   }
   PB_TRY(fg_norm2(ctx, w, n, &fs->nrm2, true));
-  return launch_fg_start(ctx, k->d_st, fs, k->d_hist, k->h_done_dev, 0, ref, k->fgm.opts.restart,
-                         k->fgm.opts.haptol, -1);
+  return launch_fg_start(ctx, k->log(), fs, 0, ref, k->fgm.opts.restart, k->fgm.opts.haptol, -1);
 }
 
 // w -= sum_j <w, v_j> v_j over the nv basis vectors, in groups of at most kMaxVecs: every group's
@@ -194,7 +191,7 @@ int pb::enqueue_fgmres_iteration(pb_ksp* k) {
   const int passes = k->fgm.opts.cgs_refinement == PB_FGMRES_REFINE_ALWAYS ? 2 : 1;
   PB_TRY(fg_orthogonalise(k, w, pos + 1, fs->dots));
   if (passes == 2) PB_TRY(fg_orthogonalise(k, w, pos + 1, fs->dots2));
-  PB_TRY(launch_fg_step(ctx, st, fs, k->d_hist, k->h_done_dev, passes, k->host_iter));
+  PB_TRY(launch_fg_step(ctx, k->log(), fs, passes, k->host_iter));
   if (pos + 1 < R) {
     k->fgm.pos = pos + 1;
     return PB_OK;
@@ -210,8 +207,7 @@ int pb::enqueue_fgmres_iteration(pb_ksp* k) {
   PB_TRY(launch_guess_diff(ctx, k->b->d, k->r, w, n));
   PB_TRY(fg_norm2(ctx, w, n, &fs->nrm2, true));
   k->fgm.pos = 0;
-  return launch_fg_start(ctx, st, fs, k->d_hist, k->h_done_dev, 1, 0, R, k->fgm.opts.haptol,
-                         k->host_iter);
+  return launch_fg_start(ctx, k->log(), fs, 1, 0, R, k->fgm.opts.haptol, k->host_iter);
 }
 
 // the solution of the cycle the solve ended in (the stream is idle: the state is final). The live

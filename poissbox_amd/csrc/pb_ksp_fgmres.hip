@@ -291,18 +291,17 @@ int launch_fg_shift(pb_ctx* ctx, double* z, const FgState* fs, const CgState* st
   return PB_OK;
 }
 
-int launch_fg_start(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_done, int mode,
-                    int ref, int restart, double haptol, int64_t host_iter) {
-  hipLaunchKernelGGL(fg_start_kernel, dim3(1), dim3(64), 0, ctx->stream, st, fs, hist, h_done,
-                     mode, ref, restart, haptol, host_iter);
+int launch_fg_start(pb_ctx* ctx, const KspLog& lg, FgState* fs, int mode, int ref, int restart,
+                    double haptol, int64_t host_iter) {
+  hipLaunchKernelGGL(fg_start_kernel, dim3(1), dim3(64), 0, ctx->stream, lg.st, fs, lg.hist,
+                     lg.h_done, mode, ref, restart, haptol, host_iter);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-int launch_fg_step(pb_ctx* ctx, CgState* st, FgState* fs, double* hist, int* h_done, int passes,
-                   int64_t host_iter) {
-  hipLaunchKernelGGL(fg_step_kernel, dim3(1), dim3(64), 0, ctx->stream, st, fs, hist, h_done,
-                     passes, host_iter);
+int launch_fg_step(pb_ctx* ctx, const KspLog& lg, FgState* fs, int passes, int64_t host_iter) {
+  hipLaunchKernelGGL(fg_step_kernel, dim3(1), dim3(64), 0, ctx->stream, lg.st, fs, lg.hist,
+                     lg.h_done, passes, host_iter);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }

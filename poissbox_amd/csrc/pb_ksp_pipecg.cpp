@@ -110,9 +110,7 @@ int pb::pipecg_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
     PB_HIP(hipMemcpyAsync(r, b->d, vb, hipMemcpyDeviceToDevice, ctx->stream));
   } else {
     PB_TRY(check_ref_norm_opts(&k->opts));
-    ref = k->opts.converged_use_initial_residual_norm
-              ? REF_INITIAL
-              : (k->opts.converged_use_min_initial_residual_norm ? REF_MIN : REF_RHS);
+    ref = k->ref_norm();
     if (ref != REF_INITIAL && !k->norm_none()) {
       if (k->norm_unp()) {
         PB_TRY(launch_pcg_sums(ctx, b->d, b->d, b->d, ps->bsums, n));
@@ -127,7 +125,7 @@ int pb::pipecg_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   PB_TRY(pcg_pc(k, r, u, nullptr, false));
   PB_TRY(op_apply_raw(k->A, u, w));
   PB_TRY(launch_pcg_sums(ctx, r, u, w, ps->sums, n));
-  return launch_pcg_finalize(ctx, k->d_st, ps, nullptr, 0, k->d_hist, k->h_done_dev, true, ref, -1);
+  return launch_pcg_finalize(ctx, k->log(), ps, nullptr, 0, true, ref, -1);
 }
 
 // One iteration at the host's count (the device's while the state is not done; every kernel that
@@ -160,6 +158,5 @@ int pb::enqueue_pipecg_iteration(pb_ksp* k) {
     PB_TRY(allreduce_device(ctx, ps->sums, kPcgSums));
     np = 0;
   }
-  return launch_pcg_finalize(ctx, st, ps, ctx->d_partials, np, k->d_hist, k->h_done_dev, false, 0,
-                             k->host_iter);
+  return launch_pcg_finalize(ctx, k->log(), ps, ctx->d_partials, np, false, 0, k->host_iter);
 }

@@ -193,11 +193,11 @@ int launch_pcg_sums(pb_ctx* ctx, const double* r, const double* u, const double*
   return pcg_reduce(ctx, nb, kPcgSums, dst);
 }
 
-int launch_pcg_finalize(pb_ctx* ctx, CgState* st, PcgState* ps, const double* parts, int nparts,
-                        double* hist, int* h_done, bool setup, int ref, int64_t host_iter) {
+int launch_pcg_finalize(pb_ctx* ctx, const KspLog& lg, PcgState* ps, const double* parts,
+                        int nparts, bool setup, int ref, int64_t host_iter) {
   ScopedTimer tm(ctx, "pipecg_finalize");
-  hipLaunchKernelGGL(pcg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, st, ps, parts,
-                     nparts, hist, h_done, setup ? 1 : 0, ref, host_iter);
+  hipLaunchKernelGGL(pcg_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, lg.st, ps, parts,
+                     nparts, lg.hist, lg.h_done, setup ? 1 : 0, ref, host_iter);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }

@@ -220,13 +220,10 @@ int pb::rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
     }
     if (k->stored_z()) PB_TRY(rich_pc(k, b->d, nullptr, &np));
     else PB_TRY(launch_rich_sums(g, b->d, k->d_st, &np));
-    return rich_finalize(ctx, np, width, nullptr, 3, k->d_st, k->d_hist, k->h_done_dev, -1, cmu,
-                         cop, rr);
+    return rich_finalize(ctx, np, width, nullptr, 3, k->log(), -1, cmu, cop, rr);
   }
   PB_TRY(check_ref_norm_opts(&k->opts));
-  const int ref = k->opts.converged_use_initial_residual_norm
-                      ? 1
-                      : (k->opts.converged_use_min_initial_residual_norm ? 2 : 0);
+  const int ref = k->ref_norm();
   const double* bsums = nullptr;
   // the reference norm ||N(M^-1 b)||: the sums of M^-1 b kept aside (unpreconditioned, Jacobi / no
   // PC: ||b|| from the same sums of dinv b; none: no reference)
@@ -240,8 +237,7 @@ int pb::rich_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   }
   PB_TRY(rich_residual(k, x->d, k->r, false, &np, &rr));
   if (k->stored_z()) PB_TRY(rich_pc(k, k->r, nullptr, &np));
-  return rich_finalize(ctx, np, width, bsums, ref, k->d_st, k->d_hist, k->h_done_dev, -1, cmu,
-                       cop, rr);
+  return rich_finalize(ctx, np, width, bsums, ref, k->log(), -1, cmu, cop, rr);
 }
 
 // one update: x_new = x + scale (M^-1 r - mean), r_new = b - A x_new, z_new and its sums, the
@@ -284,8 +280,8 @@ int pb::enqueue_rich_iteration(pb_ksp* k) {
     PB_TRY(rich_residual(k, xout, r_out, true, &np, &rr));
   }
   if (k->stored_z()) PB_TRY(rich_pc(k, r_out, &k->d_st->done, &np));
-  return rich_finalize(ctx, np, k->stored_z() ? 4 : 2, nullptr, 0, k->d_st, k->d_hist,
-                       k->h_done_dev, i, cheb ? k->ch.mu : 0.0, cheb ? k->ch.omegaprod : 0.0, rr);
+  return rich_finalize(ctx, np, k->stored_z() ? 4 : 2, nullptr, 0, k->log(), i,
+                       cheb ? k->ch.mu : 0.0, cheb ? k->ch.omegaprod : 0.0, rr);
 }
 
 // KSPSolve_PREONLY: x = N(M^-1 b). No norm, no reduction but the mean's, no NaN check. The

@@ -315,9 +315,9 @@ int rich_reduce(pb_ctx* ctx, int nparts, int width, double* dst, const RrParts& 
   return PB_OK;
 }
 
-int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref, CgState* st,
-                  double* hist, int* h_done, int64_t host_iter, double cheb_mu,
-                  double cheb_omegaprod, const RrParts& rr) {
+int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int ref,
+                  const KspLog& lg, int64_t host_iter, double cheb_mu, double cheb_omegaprod,
+                  const RrParts& rr) {
   ScopedTimer tm(ctx, "rich_finalize");  // (with its allreduce on several ranks)
   const double* parts = ctx->d_partials;
   // (the PC's own partials must have stayed below the second region)
@@ -325,14 +325,14 @@ int rich_finalize(pb_ctx* ctx, int nparts, int width, const double* bsums, int r
     return set_error(PB_ERR_UNSUPPORTED, "unpreconditioned norm: partial sums do not fit");
   if (!ctx->split) {
     hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
-                       width, ctx->d_scalars, 3, bsums, ref, st, hist, h_done, host_iter, cheb_mu,
+                       width, ctx->d_scalars, 3, bsums, ref, lg.st, lg.hist, lg.h_done, host_iter, cheb_mu,
                        cheb_omegaprod, rr);
     PB_HIP(hipGetLastError());
     return PB_OK;
   }
   PB_TRY(rich_reduce(ctx, nparts, width, nullptr, rr));
   hipLaunchKernelGGL(rich_finalize_kernel, dim3(1), dim3(256), 0, ctx->stream, parts, nparts,
-                     width, ctx->d_scalars, 2, bsums, ref, st, hist, h_done, host_iter, cheb_mu,
+                     width, ctx->d_scalars, 2, bsums, ref, lg.st, lg.hist, lg.h_done, host_iter, cheb_mu,
                      cheb_omegaprod, rr);
   PB_HIP(hipGetLastError());
   return PB_OK;

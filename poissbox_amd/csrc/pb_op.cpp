@@ -6,25 +6,17 @@ using namespace pb;
 static int star7_apply(pb_op* op, const double* x, double* y) {
   pb_grid* g = op->grid;
   const Star s = star_of(op);
-  StencilPlanes gp;
-  if (!g->ctx->split) {
-    gp.ghost_lo = x + (g->nzl - 1) * g->plane;  // periodic wrap: no copy
-    gp.ghost_hi = x;
-    return launch_star7_apply(g, s, x, y, gp, PLANES_ALL);
-  }
-  gp.ghost_lo = g->ghost_lo;
-  gp.ghost_hi = g->ghost_hi;
-  if (g->nzl < 3) {
-    PB_TRY(halo_exchange(g, x, x + (g->nzl - 1) * g->plane));
-    return launch_star7_apply(g, s, x, y, gp, PLANES_ALL);
-  }
-  // interior planes overlap the halo exchange; the two boundary planes follow it (timed as one
-  // apply: interior launch, wait for the exchange, boundary launch)
-  ScopedTimer tm(g->ctx, "stencil");
-  PB_TRY(halo_begin(g, x, x + (g->nzl - 1) * g->plane));
-  PB_TRY(launch_star7_apply(g, s, x, y, gp, PLANES_INTERIOR));
-  PB_TRY(halo_end(g));
-  return launch_star7_apply(g, s, x, y, gp, PLANES_BOUNDARY);
+  const double* hi = x + (g->nzl - 1) * g->plane;
+  StencilPlanes one;
+  one.ghost_lo = hi;  // periodic wrap: no copy
+  one.ghost_hi = x;
+  // split grids: interior planes overlap the halo exchange; the two boundary planes follow it
+  // (timed as one apply: interior launch, wait for the exchange, boundary launch)
+  int none = 0;  // (no sums)
+  return halo_overlap(g, x, hi, one, "stencil", 0, &none,
+                      [&](int mode, const StencilPlanes& gp, int, int*) {
+                        return launch_star7_apply(g, s, x, y, gp, mode);
+                      });
 }
 
 int pb::op_apply_raw(pb_op* op, const double* x, double* y) {

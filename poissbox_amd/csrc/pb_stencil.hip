@@ -24,7 +24,7 @@ struct StoreY {
 
 // Timer names: a whole-grid launch is "<name>"; the two launches of a split apply (interior
 // planes, then the boundary planes after the halo exchange) are "<name>_interior" and
-// "<name>_boundary", and the caller times the apply as a whole under "<name>" (pb_solver.cpp),
+// "<name>_boundary", and halo_overlap (pb_internal.hpp) times the apply as a whole under "<name>",
 // so "<name>" always averages complete applies over all owned planes.
 const char* timer_name(int mode, const char* all, const char* interior, const char* boundary) {
   return mode == PLANES_ALL ? all : (mode == PLANES_INTERIOR ? interior : boundary);
