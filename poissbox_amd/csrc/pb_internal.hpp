@@ -745,7 +745,7 @@ int launch_cheb_x(pb_grid* g, const double* y, const double* ym1, const double* 
 int launch_pre_scale_sum(pb_grid* g, const double* src, double* dst, double dinv, int* nparts);
 int launch_pre_shift(pb_grid* g, double* x, double ntot);
 
-// ---- geometric multigrid / red-black SOR preconditioner (pb_mg.hip) ----
+// ---- geometric multigrid / red-black SOR preconditioner (pb_mg.cpp; its types: pb_mg.hpp) ----
 struct Mg;
 // levels_req: 0 = automatic; pc_type PB_PC_SOR (one symmetric red-black sweep) or PB_PC_MG
 int mg_create(pb_grid* g, const double deltas[3], int pc_type, int levels_req, int coarse_its,

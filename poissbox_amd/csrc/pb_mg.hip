@@ -22,80 +22,19 @@
 // the tests compare bit for bit.
 //
 // Selectable level smoothers (pb_pc_mg_opts, -mg_levels_*): nu sweeps per leg, and damped Jacobi or
-// Chebyshev over Jacobi instead of SOR (mg_apply_levels at the end of this file; restated in
-// tests/mg_smoothers_restatement.py). The default -- richardson + sor, one sweep -- is mg_apply's
-// fused path above, unchanged.
+// Chebyshev over Jacobi instead of SOR (mg_poly_kernel, mg_poly_x_kernel; restated in
+// tests/mg_smoothers_restatement.py).
+//
+// This file: the per-pair, per-cell, polynomial and tail kernels and, at its end, the launchers
+// that name them, one per pass (pb_mg.hpp). The host path -- hierarchy, level plan, driver and
+// legs -- is pb_mg.cpp; the fused sweeps are pb_mg_sweep.hip, the engine passes pb_mg_engine.hip.
 #include <algorithm>
-#include <cmath>
-#include <vector>
+#include <type_traits>
 
 #include "pb_device.hpp"
+#include "pb_mg.hpp"
 
 namespace pb {
-
-struct MgGeo {
-  int nx, ny, nzl;
-  int64_t plane, nlocal, k0;
-};
-
-struct MgLevel {
-  int64_t n[3];
-  double h[3];
-  Star s;
-  pb_grid* g = nullptr;  // level grid (level 0: the caller's grid)
-  bool own = false;
-  double* x = nullptr;    // correction (level 0: the PC output z)
-  double* b = nullptr;    // right-hand side (level 0: the PC input r)
-  double* res = nullptr;  // residual scratch
-  // fused post-smoothing (one rank, large levels): the pre-smoothed x, kept apart from x so that
-  // the prolongation + both half-sweeps can read it and write x in one pass
-  double* xs = nullptr;
-  // Jacobi-type smoothers (mg_set_smoother): two more iterate buffers and one more residual
-  // buffer -- a step forms y_new at a point's neighbours from y, y_prev and r there, so it writes
-  // to buffers it does not read; x, t1, t2 and res, r2 rotate
-  double* t1 = nullptr;
-  double* t2 = nullptr;
-  double* r2 = nullptr;
-  MgGeo geo() const {
-    return MgGeo{(int)g->n[0], (int)g->n[1], (int)g->nzl, g->plane, g->nlocal, g->k0};
-  }
-};
-
-struct Mg {
-  pb_ctx* ctx = nullptr;
-  std::vector<MgLevel> lv;
-  double omega = 1.0;
-  int coarse_its = 1;
-  double* mem = nullptr;
-  const int* skip = nullptr;  // device flag: when set, the kernels of this apply exit at entry
-  // SOR half-sweeps and residuals of levels whose planes hold >= engine_min_plane points run on
-  // the z-marching stencil engine (PB_MG_ENGINE_MIN_PLANE; smaller levels: per-pair kernels,
-  // whose short z-chunks would not amortise the engine's prologue)
-  int64_t engine_min_plane = 256 * 256;
-  // restriction and prolongation: one thread per coarse column marching in z on coarse levels of
-  // >= restrict_z_min_cols columns, one thread per coarse cell (prolongation) / point
-  // (restriction) below
-  int64_t restrict_z_min_cols = 4096;
-  bool tail_attr = false;  // mg_tail_kernel's dynamic-LDS limit raised
-  // Decomposed grids (r04): the coarse levels [La, L) are gathered onto every rank once per
-  // V-cycle (one all-to-all of level La's right-hand side) and run there as the one-launch tail
-  // on full-grid arrays -- instead of a latency-bound halo exchange per half-sweep, residual and
-  // transfer on levels of a few thousand points. La = 0: none. Every rank computes the same
-  // coarse correction (same kernels, same inputs) and prolongates from its own planes of it.
-  int La = 0;
-  double* agg = nullptr;                   // full-grid x, b, res of levels La .. L-1; send staging
-  std::vector<MgGeo> ageo;                 // their full-grid geometry (k0 = 0)
-  std::vector<double*> ax, ab, ares;
-  double* agg_send = nullptr;              // P copies of this rank's level-La slab
-  std::vector<int64_t> agg_sc, agg_rc;     // all-to-all counts (send: own slab; recv: rank q's)
-  // the level smoother (pb_pc_mg_opts). custom(): anything but the default richardson + sor with
-  // one sweep per leg -- runs mg_apply_levels (per-level launches; no fused SOR passes, no tail,
-  // no agglomeration)
-  MgSmoother sm;
-  bool poly() const { return sm.pc == PB_MG_LEVELS_JACOBI; }
-  bool custom() const { return poly() || sm.nu > 1; }
-  double* pmem = nullptr;  // the levels' t1, t2, r2
-};
 
 // ---------------------------------------------------------------------------------------------
 // kernels. Every level has an even x extent, so one thread owns an (i even, i + 1) pair: 16-byte
@@ -128,14 +67,13 @@ struct Nb4 {
   double zm, ym, yp, zp;
 };
 __device__ __forceinline__ Nb4 nb4(const MgGeo& G, const double* v, const double* lo,
-                                   const double* hi, int64_t id, int i, int j, int k) {
+                                   const double* hi, int64_t id, int j, int k) {
   const int64_t pid = id - (int64_t)k * G.plane;
   Nb4 r;
   r.zm = k > 0 ? v[id - G.plane] : lo[pid];
   r.zp = k < G.nzl - 1 ? v[id + G.plane] : hi[pid];
   r.ym = v[id + (int64_t)(wrapm(j - 1, G.ny) - j) * G.nx];
   r.yp = v[id + (int64_t)(wrapm(j + 1, G.ny) - j) * G.nx];
-  (void)i;
   return r;
 }
 
@@ -148,10 +86,12 @@ __device__ __forceinline__ double red0(double b, const Star& s, double omega) {
 // mode 0: one red-black SOR half-sweep over `color` (x holds the current iterate).
 // mode 1: the first two half-sweeps from x = 0 fused: red = w D^-1 b, then black from those red
 //         values, computed from b directly (lo / hi are then b's ghost planes).
-__device__ __forceinline__ void mg_smooth_body(MgGeo G, double* x, const double* __restrict__ b, const double* lo, const double* hi, Star s, double omega, int color, int mode, int64_t t0, int64_t ts) {
+__device__ __forceinline__ void mg_smooth_body(MgGeo G, double* x, const double* __restrict__ b,
+                                               const double* lo, const double* hi, Star s,
+                                               double omega, int color, int mode, int64_t t0,
+                                               int64_t ts) {
   const int64_t npairs = G.nlocal >> 1;
-  for (int64_t q = t0; q < npairs;
-       q += ts) {
+  for (int64_t q = t0; q < npairs; q += ts) {
     const PairPos P = pair_pos(G, q);
     const int64_t row = P.idx - P.i0;
     if (mode == 1) {
@@ -161,7 +101,7 @@ __device__ __forceinline__ void mg_smooth_body(MgGeo G, double* x, const double*
       const int64_t idb = row + ib;
       const double bb = dr ? bp.x : bp.y;               // black point's b
       const double br = dr ? bp.y : bp.x;
-      const Nb4 n4 = nb4(G, b, lo, hi, idb, ib, P.j, P.k);
+      const Nb4 n4 = nb4(G, b, lo, hi, idb, P.j, P.k);
       const double bxm = ib == P.i0 + 1 ? bp.x : b[row + wrapm(ib - 1, G.nx)];
       const double bxp = ib == P.i0 ? bp.y : b[row + wrapm(ib + 1, G.nx)];
       double nb = s.cz * red0(n4.zm, s, omega);
@@ -183,7 +123,7 @@ __device__ __forceinline__ void mg_smooth_body(MgGeo G, double* x, const double*
     const int d = (int)((color + P.j + G.k0 + P.k) & 1);  // offset of the updated point
     const int ic = P.i0 + d;
     const int64_t id = row + ic;
-    const Nb4 n4 = nb4(G, x, lo, hi, id, ic, P.j, P.k);
+    const Nb4 n4 = nb4(G, x, lo, hi, id, P.j, P.k);
     const double xm = d ? xp.x : x[row + wrapm(P.i0 - 1, G.nx)];
     const double xq = d ? x[row + wrapm(P.i0 + 2, G.nx)] : xp.y;
     double nb = s.cz * n4.zm;
@@ -207,15 +147,43 @@ __global__ __launch_bounds__(256) void mg_smooth_kernel(MgGeo G, double* x,
                                                         double omega, int color, int mode,
                                                         const int* skip) {
   if (skip && *skip) return;
-  mg_smooth_body(G, x, b, lo, hi, s, omega, color, mode, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                  (int64_t)gridDim.x * blockDim.x);
+  mg_smooth_body(G, x, b, lo, hi, s, omega, color, mode,
+                 (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-// res = b - A x for both points of the pair (the reference operator's summation order)
-__device__ __forceinline__ void mg_residual_body(MgGeo G, const double* __restrict__ x, const double* __restrict__ b, const double* __restrict__ lo, const double* __restrict__ hi, Star s, double* __restrict__ res, int64_t t0, int64_t ts) {
+// b - A x at both points of a pair (the reference operator's summation order): xc the pair, zm,
+// zp, ym, yp its neighbour pairs, xl / xr the points left and right of it
+__device__ __forceinline__ dv2 residual_pair(const Star& s, dv2 bc, dv2 xc, dv2 zm, dv2 zp, dv2 ym,
+                                             dv2 yp, double xl, double xr) {
+  double a0 = s.cz * zm.x;
+  a0 = a0 + s.cy * ym.x;
+  a0 = a0 + s.cx * xl;
+  a0 = a0 + s.cc * xc.x;
+  a0 = a0 + s.cx * xc.y;
+  a0 = a0 + s.cy * yp.x;
+  a0 = a0 + s.cz * zp.x;
+  double a1 = s.cz * zm.y;
+  a1 = a1 + s.cy * ym.y;
+  a1 = a1 + s.cx * xc.x;
+  a1 = a1 + s.cc * xc.y;
+  a1 = a1 + s.cx * xr;
+  a1 = a1 + s.cy * yp.y;
+  a1 = a1 + s.cz * zp.y;
+  dv2 o;
+  o.x = bc.x - a0;
+  o.y = bc.y - a1;
+  return o;
+}
+
+// res = b - A x for both points of the pair
+__device__ __forceinline__ void mg_residual_body(MgGeo G, const double* __restrict__ x,
+                                                 const double* __restrict__ b,
+                                                 const double* __restrict__ lo,
+                                                 const double* __restrict__ hi, Star s,
+                                                 double* __restrict__ res, int64_t t0,
+                                                 int64_t ts) {
   const int64_t npairs = G.nlocal >> 1;
-  for (int64_t q = t0; q < npairs;
-       q += ts) {
+  for (int64_t q = t0; q < npairs; q += ts) {
     const PairPos P = pair_pos(G, q);
     const int64_t row = P.idx - P.i0;
     const dv2 xc = *(const dv2*)(x + P.idx);
@@ -227,24 +195,7 @@ __device__ __forceinline__ void mg_residual_body(MgGeo G, const double* __restri
     const dv2 yp = *(const dv2*)(x + P.idx + (int64_t)(wrapm(P.j + 1, G.ny) - P.j) * G.nx);
     const double xl = x[row + wrapm(P.i0 - 1, G.nx)];
     const double xr = x[row + wrapm(P.i0 + 2, G.nx)];
-    double a0 = s.cz * zm.x;
-    a0 = a0 + s.cy * ym.x;
-    a0 = a0 + s.cx * xl;
-    a0 = a0 + s.cc * xc.x;
-    a0 = a0 + s.cx * xc.y;
-    a0 = a0 + s.cy * yp.x;
-    a0 = a0 + s.cz * zp.x;
-    double a1 = s.cz * zm.y;
-    a1 = a1 + s.cy * ym.y;
-    a1 = a1 + s.cx * xc.x;
-    a1 = a1 + s.cc * xc.y;
-    a1 = a1 + s.cx * xr;
-    a1 = a1 + s.cy * yp.y;
-    a1 = a1 + s.cz * zp.y;
-    dv2 o;
-    o.x = bc.x - a0;
-    o.y = bc.y - a1;
-    *(dv2*)(res + P.idx) = o;
+    *(dv2*)(res + P.idx) = residual_pair(s, bc, xc, zm, zp, ym, yp, xl, xr);
   }
 }
 __global__ __launch_bounds__(256) void mg_residual_kernel(MgGeo G, const double* __restrict__ x,
@@ -254,7 +205,7 @@ __global__ __launch_bounds__(256) void mg_residual_kernel(MgGeo G, const double*
                                                           double* __restrict__ res, const int* skip) {
   if (skip && *skip) return;
   mg_residual_body(G, x, b, lo, hi, s, res, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                  (int64_t)gridDim.x * blockDim.x);
+                   (int64_t)gridDim.x * blockDim.x);
 }
 
 __device__ __forceinline__ void mg_ijk(const MgGeo& G, int64_t idx, int& i, int& j, int& k) {
@@ -265,11 +216,15 @@ __device__ __forceinline__ void mg_ijk(const MgGeo& G, int64_t idx, int& i, int&
   j = (int)(row - (uint32_t)k * (uint32_t)G.ny);
 }
 
-// b_c = R res_f, R = P^T / 8: 4 x 4 x 4 fine cells (2I-1 .. 2I+2 per direction)
-__device__ __forceinline__ void mg_restrict_body(MgGeo F, const double* __restrict__ rf, const double* __restrict__ lo, const double* __restrict__ hi, MgGeo Cg, double* __restrict__ bc, int64_t t0, int64_t ts) {
+// b_c = R res_f, R = P^T / 8: 4 x 4 x 4 fine cells (2I-1 .. 2I+2 per direction). (The x-y sum is
+// restrict_xy's below, written out: calling it here changes this kernel's and the tail's code)
+__device__ __forceinline__ void mg_restrict_body(MgGeo F, const double* __restrict__ rf,
+                                                 const double* __restrict__ lo,
+                                                 const double* __restrict__ hi, MgGeo Cg,
+                                                 double* __restrict__ bc, int64_t t0,
+                                                 int64_t ts) {
   const double w[4] = {0.125, 0.375, 0.375, 0.125};
-  for (int64_t idx = t0; idx < Cg.nlocal;
-       idx += ts) {
+  for (int64_t idx = t0; idx < Cg.nlocal; idx += ts) {
     int I, J, K;
     mg_ijk(Cg, idx, I, J, K);
     const int xl = wrapm(2 * I - 1, F.nx), xr = wrapm(2 * I + 2, F.nx);
@@ -300,7 +255,7 @@ __global__ __launch_bounds__(256) void mg_restrict_kernel(MgGeo F, const double*
                                                           double* __restrict__ bc, const int* skip) {
   if (skip && *skip) return;
   mg_restrict_body(F, rf, lo, hi, Cg, bc, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                  (int64_t)gridDim.x * blockDim.x);
+                   (int64_t)gridDim.x * blockDim.x);
 }
 
 // The same restriction, one thread per coarse (I, J) column marching over a chunk of coarse
@@ -357,13 +312,16 @@ __global__ __launch_bounds__(256) void mg_restrict_z_kernel(MgGeo F, const doubl
   }
 }
 
-// x_f += P x_c (trilinear, cell-centred: near parent 3/4, far 1/4), one thread per coarse cell: its 2 x 2 x 2 fine children from the
-// 3 x 3 x 3 coarse neighbourhood (each child by the formula above, same operation order), so a
-// fine row pair is read and written with 16-byte accesses and each coarse value is fetched
-// ~27/8 times per fine point instead of 6.
-__device__ __forceinline__ void mg_prolong_cell_body(MgGeo F, double* __restrict__ xf, MgGeo Cg, const double* __restrict__ xc, const double* __restrict__ lo, const double* __restrict__ hi, int64_t t0, int64_t ts) {
-  for (int64_t idx = t0; idx < Cg.nlocal;
-       idx += ts) {
+// x_f += P x_c (trilinear, cell-centred: near parent 3/4, far 1/4), one thread per coarse cell:
+// its 2 x 2 x 2 fine children from the 3 x 3 x 3 coarse neighbourhood (each child by the formula
+// above, same operation order), so a fine row pair is read and written with 16-byte accesses and
+// each coarse value is fetched ~27/8 times per fine point instead of 6.
+__device__ __forceinline__ void mg_prolong_cell_body(MgGeo F, double* __restrict__ xf, MgGeo Cg,
+                                                     const double* __restrict__ xc,
+                                                     const double* __restrict__ lo,
+                                                     const double* __restrict__ hi, int64_t t0,
+                                                     int64_t ts) {
+  for (int64_t idx = t0; idx < Cg.nlocal; idx += ts) {
     int I, J, K;
     mg_ijk(Cg, idx, I, J, K);
     const int Im = wrapm(I - 1, Cg.nx), Ip = wrapm(I + 1, Cg.nx);
@@ -402,7 +360,7 @@ __global__ __launch_bounds__(256) void mg_prolong_cell_kernel(MgGeo F, double* _
                                                               const int* skip) {
   if (skip && *skip) return;
   mg_prolong_cell_body(F, xf, Cg, xc, lo, hi, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                  (int64_t)gridDim.x * blockDim.x);
+                       (int64_t)gridDim.x * blockDim.x);
 }
 
 // The same prolongation, one thread per coarse (I, J) column marching over a chunk of coarse
@@ -557,24 +515,7 @@ __global__ __launch_bounds__(256) void mg_poly_kernel(MgGeo G, PolyArgs A,
     const dv2 yp = poly_pair<N>(A, P.idx + (int64_t)(wrapm(P.j + 1, G.ny) - P.j) * G.nx);
     const double xl = poly_at<N>(A, row + wrapm(P.i0 - 1, G.nx));
     const double xr = poly_at<N>(A, row + wrapm(P.i0 + 2, G.nx));
-    double a0 = s.cz * zm.x;
-    a0 = a0 + s.cy * ym.x;
-    a0 = a0 + s.cx * xl;
-    a0 = a0 + s.cc * xc.x;
-    a0 = a0 + s.cx * xc.y;
-    a0 = a0 + s.cy * yp.x;
-    a0 = a0 + s.cz * zp.x;
-    double a1 = s.cz * zm.y;
-    a1 = a1 + s.cy * ym.y;
-    a1 = a1 + s.cx * xc.x;
-    a1 = a1 + s.cc * xc.y;
-    a1 = a1 + s.cx * xr;
-    a1 = a1 + s.cy * yp.y;
-    a1 = a1 + s.cz * zp.y;
-    dv2 o;
-    o.x = bc.x - a0;
-    o.y = bc.y - a1;
-    *(dv2*)(r_out + P.idx) = o;
+    *(dv2*)(r_out + P.idx) = residual_pair(s, bc, xc, zm, zp, ym, yp, xl, xr);
     *(dv2*)(y_out + P.idx) = xc;
   }
 }
@@ -594,7 +535,6 @@ struct TailLevel {
   Star s;
   int64_t ox, ob, ores;  // LDS offsets (doubles) of x, b, res when the tail runs in LDS
 };
-static constexpr int kTailMax = 12;
 static constexpr size_t kTailLdsMax = 144 * 1024;  // LDS the tail may take (of 160 KB per CU)
 struct TailArgs {
   TailLevel lv[kTailMax];
@@ -683,12 +623,10 @@ static int transfer_chunk(pb_ctx* ctx, int64_t cols, int64_t nzl, int64_t* nchun
   return kc;
 }
 
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
+// ---- the launchers (pb_mg.hpp): each kernel above is named here once; engine or pair kernel,
+// marching or per-cell transfer is the level's LevelPlan's to say (pb_mg.cpp) ----
 // one thread per item (no grid-stride loop unless the grid would exceed 2^30 blocks)
-static int mg_blocks(pb_ctx* ctx, int64_t n) {
-  (void)ctx;
+static int mg_blocks(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (int)std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)1 << 30));
 }
@@ -707,476 +645,86 @@ static int ghosts(MgLevel& L, const double* v, const double** lo, const double**
   return PB_OK;
 }
 
-// mode 0: half-sweep of `color`; mode 1: zero-initialised red + black half-sweeps fused.
-// sums_st (mode 0, engine path only): also take CG's residual sums of the output (*nparts set)
-static int smooth(Mg* mg, MgLevel& L, int color, int mode, const CgState* sums_st = nullptr,
-                  int* nparts = nullptr) {
+int level_smooth(Mg* mg, MgLevel& L, int color, int mode, MgSums sums) {
   const double *lo = nullptr, *hi = nullptr;
   PB_TRY(ghosts(L, mode == 1 ? L.b : L.x, &lo, &hi));
-  if (L.g->plane >= mg->engine_min_plane) {
+  if (L.plan.engine) {
     const StencilPlanes gp{lo, hi};
     return launch_mg_sor(L.g, L.s, L.x, L.b, gp, mg->omega, color, mode == 1, mg->skip,
-                         mode == 0 ? sums_st : nullptr, mode == 0 ? nparts : nullptr);
+                         mode == 0 ? sums.st : nullptr, mode == 0 ? sums.nparts : nullptr);
   }
   const MgGeo G = L.geo();
-  hipLaunchKernelGGL(mg_smooth_kernel, dim3(mg_blocks(mg->ctx, G.nlocal / 2)), dim3(256), 0,
+  hipLaunchKernelGGL(mg_smooth_kernel, dim3(mg_blocks(G.nlocal / 2)), dim3(256), 0,
                      mg->ctx->stream, G, L.x, (const double*)L.b, lo, hi, L.s, mg->omega, color,
                      mode, mg->skip);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-// coarsest level: `coarse_its` symmetric red-black sweeps from zero (red, black, red, black, ...)
-static int coarse_solve(Mg* mg, MgLevel& L, const CgState* sums_st, int* nparts) {
-  PB_TRY(smooth(mg, L, 0, 1));  // red from zero + black
-  const int its = mg->coarse_its;
-  PB_TRY(smooth(mg, L, 0, 0, its == 1 ? sums_st : nullptr, nparts));
-  for (int it = 1; it < its; ++it) {
-    PB_TRY(smooth(mg, L, 1, 0));
-    PB_TRY(smooth(mg, L, 0, 0, it == its - 1 ? sums_st : nullptr, nparts));
-  }
-  return PB_OK;
-}
-
-int mg_plan_levels(const int64_t n[3], int nranks, int levels_req) {
-  std::vector<int64_t> k0(nranks), nz(nranks);
-  for (int r = 0; r < nranks; ++r) pb_slab_partition(n[2], nranks, r, &k0[r], &nz[r]);
-  int64_t cur[3] = {n[0], n[1], n[2]};
-  int L = 1;
-  const int cap = levels_req > 0 ? levels_req : 64;
-  while (L < cap) {
-    bool ok = true;
-    for (int d = 0; d < 3; ++d) ok = ok && cur[d] % 4 == 0;  // coarse extents stay even
-    if (levels_req <= 0) ok = ok && std::min(cur[0], std::min(cur[1], cur[2])) > 4;
-    for (int r = 0; r < nranks; ++r) ok = ok && k0[r] % 2 == 0 && nz[r] % 2 == 0;
-    if (!ok) break;
-    for (int d = 0; d < 3; ++d) cur[d] /= 2;
-    for (int r = 0; r < nranks; ++r) {
-      k0[r] /= 2;
-      nz[r] /= 2;
-    }
-    ++L;
-  }
-  return L;
-}
-
-int mg_levels(const Mg* mg) { return (int)mg->lv.size(); }
-
-void mg_destroy(Mg* mg) {
-  if (!mg) return;
-  (void)wait_stream(mg->ctx, mg->ctx->stream, "mg_destroy");
-  for (auto& L : mg->lv)
-    if (L.own) pb_grid_destroy(L.g);
-  if (mg->mem) (void)hipFree(mg->mem);
-  if (mg->agg) (void)hipFree(mg->agg);
-  if (mg->pmem) (void)hipFree(mg->pmem);
-  delete mg;
-}
-
-// levels whose planes hold at least this many points run the fused / engine passes: 256^2 on one
-// rank (the 128^3 level's six per-level launches beat the fused passes there, 0.381 vs 0.409 ms);
-// 128^2 on decomposed grids, where every per-level pass costs a halo exchange (force_comm 512^3
-// MG-PCG 48.1 -> 47.75 ms, profiles/r04/decomposed/mg_engine_128_ab.txt)
-static int64_t mg_engine_min_plane_default(const pb_ctx* ctx) {
-  return ctx->split ? 128 * 128 : 256 * 256;
-}
-
-// the agglomerated coarse levels of a decomposed grid (Mg::La): the first level whose whole grid
-// fits the one-launch tail (<= mg_agglomerate_max points, default PB_MG_TAIL_MAX as on one
-// rank), at least level 1. Only with an all-to-all to gather them (RCCL, or a host transport
-// with an alltoallv callback): the built-in shm transport keeps the halo-exchange levels
-static int mg_agglomerate_setup(Mg* mg) {
-  pb_ctx* ctx = mg->ctx;
-  const int L = (int)mg->lv.size();
-  mg->La = 0;
-  if (!ctx->split || L < 2 || !tune("mg_agglomerate", 1)) return PB_OK;
-  if (!ctx->comm && !ctx->h_alltoallv) return PB_OK;
-  const int64_t tail_max = tune("mg_tail_max", 8192);
-  int La = L;
-  for (int l = L - 1; l >= 1; --l) {
-    const MgLevel& v = mg->lv[l];
-    if (v.n[0] * v.n[1] * v.n[2] <= tail_max) La = l;
-    else break;
-  }
-  if (La >= L || L - La > kTailMax) return PB_OK;
-  const int P = ctx->nranks;
-  const MgLevel& A0 = mg->lv[La];
-  int64_t total = 0;
-  for (int l = La; l < L; ++l) {
-    const MgLevel& v = mg->lv[l];
-    total += 3 * ((v.n[0] * v.n[1] * v.n[2] + 1) & ~(int64_t)1);
-  }
-  const int64_t slab = A0.g->nlocal;
-  total += P * slab;
-  if (hipMalloc(&mg->agg, (size_t)total * sizeof(double)) != hipSuccess)
-    return set_error(PB_ERR_ALLOC, "multigrid coarse levels: out of device memory");
-  double* q = mg->agg;
-  for (int l = La; l < L; ++l) {
-    const MgLevel& v = mg->lv[l];
-    const int64_t n = v.n[0] * v.n[1] * v.n[2], n2 = (n + 1) & ~(int64_t)1;
-    mg->ageo.push_back(MgGeo{(int)v.n[0], (int)v.n[1], (int)v.n[2], v.n[0] * v.n[1], n, 0});
-    mg->ax.push_back(q);
-    mg->ab.push_back(q + n2);
-    mg->ares.push_back(q + 2 * n2);
-    q += 3 * n2;
-  }
-  mg->agg_send = q;
-  mg->agg_sc.assign(P, slab);
-  mg->agg_rc.resize(P);
-  for (int r = 0; r < P; ++r) {
-    int64_t k0 = 0, nz = 0;
-    pb_slab_partition(mg->lv[0].g->n[2], P, r, &k0, &nz);
-    mg->agg_rc[r] = (nz >> La) * A0.n[0] * A0.n[1];
-  }
-  mg->La = La;
-  return PB_OK;
-}
-
-int mg_create(pb_grid* g, const double deltas[3], int pc_type, int levels_req, int coarse_its,
-              double omega, Mg** out) {
-  pb_ctx* ctx = g->ctx;
-  for (int d = 0; d < 3; ++d)
-    if (g->n[d] % 2)
-      return set_error(PB_ERR_UNSUPPORTED,
-                       "red-black SOR / multigrid needs even grid extents (got %lld x %lld x %lld)",
-                       (long long)g->n[0], (long long)g->n[1], (long long)g->n[2]);
-  if (g->nlocal >= ((int64_t)1 << 32))
-    return set_error(PB_ERR_UNSUPPORTED, "multigrid: more than 2^32 points on one GPU");
-  // PETSc PCSORSetOmega rejects omega outside (0, 2); PB_SOR_OMEGA_ANY=1 (diagnostics) accepts
-  // it -- an indefinite SOR preconditioner, e.g. to exercise KSP_DIVERGED_INDEFINITE_PC
-  if (!(omega > 0.0 && omega < 2.0) && !tune("sor_omega_any", 0))
-    return set_error(PB_ERR_ARG, "SOR omega must be in (0, 2)");
-  Mg* mg = new Mg();
-  mg->ctx = ctx;
-  mg->omega = omega;
-  const int L = pc_type == PB_PC_MG ? mg_plan_levels(g->n, ctx->nranks, levels_req) : 1;
-  mg->coarse_its = pc_type == PB_PC_MG ? std::max(1, coarse_its) : 1;
-  mg->lv.resize(L);
-  int64_t total = 0;
-  // levels that take the fused post-smoothing (PB_MG_POST_FUSED, one rank): an xs array each
-  // (N ranks: the unrolled fused passes with deep ghost planes, r04; mg_split_fused = 0 keeps
-  // the decomposed V-cycle on the per-pass kernels)
-  const bool want_post = !ctx->split || tune("mg_split_fused", 1) != 0;
-  const int64_t post_min_plane = tune("mg_engine_min_plane", mg_engine_min_plane_default(ctx));
-  auto takes_post = [&](const MgLevel& lv, int l) {
-    return want_post && l < L - 1 && lv.g->plane >= post_min_plane && sor_sweep2_supported(lv.g);
-  };
-  for (int l = 0; l < L; ++l) {
-    MgLevel& lv = mg->lv[l];
-    for (int d = 0; d < 3; ++d) {
-      lv.n[d] = g->n[d] >> l;
-      lv.h[d] = deltas[d] * (double)(1 << l);
-    }
-    lv.s = star_coeffs(lv.h);
-    if (l == 0) {
-      lv.g = g;
-    } else {
-      const int rc = grid_create_part(ctx, lv.n, g->L, g->k0 >> l, g->nzl >> l, &lv.g);
-      if (rc != PB_OK) {
-        mg_destroy(mg);
-        return rc;
-      }
-      lv.own = true;
-      total += 2 * lv.g->nlocal;  // x, b
-    }
-    if (l < L - 1) total += lv.g->nlocal;  // residual
-    if (takes_post(lv, l)) total += lv.g->nlocal;
-  }
-  if (total > 0 && hipMalloc(&mg->mem, (size_t)total * sizeof(double)) != hipSuccess) {
-    mg_destroy(mg);
-    return set_error(PB_ERR_ALLOC, "multigrid levels: out of device memory");
-  }
-  double* p = mg->mem;
-  for (int l = 0; l < L; ++l) {
-    MgLevel& lv = mg->lv[l];
-    if (l > 0) {
-      lv.x = p;
-      p += lv.g->nlocal;
-      lv.b = p;
-      p += lv.g->nlocal;
-    }
-    if (l < L - 1) {
-      lv.res = p;
-      p += lv.g->nlocal;
-    }
-    if (takes_post(lv, l)) {
-      lv.xs = p;
-      p += lv.g->nlocal;
-    }
-  }
-  if (const int rc = mg_agglomerate_setup(mg); rc != PB_OK) {
-    mg_destroy(mg);
-    return rc;
-  }
-  *out = mg;
-  return PB_OK;
-}
-
-// level l pre-smooths into xs and post-smooths with the fused prolongation kernel: it has an xs
-// array (mg_create), the fused pre-smoothing applies, and so does the marching prolongation
-static bool post_fused(const Mg* mg, int l) {
-  const MgLevel& F = mg->lv[l];
-  if (!F.xs || l + 1 >= (int)mg->lv.size() || F.g->plane < mg->engine_min_plane) return false;
-  const MgLevel& C = mg->lv[l + 1];
-  // N ranks: the unrolled kernel with deep ghosts (even slab origin, >= 2 planes per slab)
-  if (mg->ctx->split && (!tune("mg_split_fused", 1) || F.g->k0 % 2 || F.g->nzl < 2 ||
-                         C.g->nzl < 2))
-    return false;
-  return C.g->n[0] * C.g->n[1] >= mg->restrict_z_min_cols;
-}
-
-static int mg_apply_levels(Mg* mg, const double* r, double* z, const int* skip);
-
-int mg_apply(Mg* mg, const double* r, double* z, const int* skip, const CgState* sums_st,
-             int* nparts) {
-  if (nparts) *nparts = 0;
-  if (mg->custom()) return mg_apply_levels(mg, r, z, skip);  // (the caller takes CG's sums)
-  ScopedTimer tm(mg->ctx, "mg_apply");
-  mg->skip = skip;
-  mg->engine_min_plane = tune("mg_engine_min_plane", mg_engine_min_plane_default(mg->ctx));
-  mg->restrict_z_min_cols = tune("mg_restrict_z_min_cols", 4096);
-  const int L = (int)mg->lv.size();
-  mg->lv[0].b = const_cast<double*>(r);
-  mg->lv[0].x = z;
-  pb_ctx* ctx = mg->ctx;
-  // the coarse tail in one launch (one rank): levels Lt .. L-1 of <= PB_MG_TAIL_MAX points
-  int Lt = L;
-  if (mg->La > 0) Lt = mg->La;  // decomposed grid: the agglomerated levels run as the tail
-  else if (!ctx->split) {
-    const int64_t tail_max = tune("mg_tail_max", 8192);
-    Lt = L - 1;
-    while (Lt > 1 && mg->lv[Lt - 1].g->nlocal <= tail_max) --Lt;
-    if (Lt < 1 || mg->lv[Lt].g->nlocal > tail_max || L - Lt > kTailMax) Lt = L;
-  }
-  const int Ldown = Lt < L ? Lt : L - 1;  // host down-legs l < Ldown
-  for (int l = 0; l < Ldown; ++l) {  // down: pre-smooth (red, black), residual, restrict
-    MgLevel& F = mg->lv[l];
-    MgLevel& Cl = mg->lv[l + 1];
-    // large level: zero-start red + black half-sweeps and the residual in one pass
-    const bool fused = F.g->plane >= mg->engine_min_plane && sor_sweep2_supported(F.g);
-    // one rank: the restriction too (the residual is never stored)
-    const bool fused_r = fused && F.g->nzl % 2 == 0 &&
-                         (!ctx->split || (tune("mg_split_fused", 1) && F.g->nzl >= 3 &&
-                                          F.g->k0 % 2 == 0));
-    if (fused_r) {
-      ScopedTimer t1(ctx, l == 0 ? "mg_fine_smooth_first" : "mg_coarse_levels");
-      PB_TRY(launch_presmooth_restrict(F.g, F.s, Cl.g, F.b, post_fused(mg, l) ? F.xs : F.x, Cl.b,
-                                       mg->omega, mg->skip));
-      continue;
-    }
-    {
-      ScopedTimer t1(ctx, l == 0 ? "mg_fine_smooth_first" : "mg_coarse_levels");
-      if (fused)
-        PB_TRY(launch_presmooth_residual(F.g, F.s, F.b, post_fused(mg, l) ? F.xs : F.x, F.res,
-                                         mg->omega, mg->skip));
-      else
-        PB_TRY(smooth(mg, F, 0, 1));  // red from zero + black
-    }
-    ScopedTimer t2(ctx, l == 0 ? "mg_fine_resid_restrict" : "mg_coarse_levels");
-    const double *lo, *hi;
-    const MgGeo G = F.geo();
-    if (fused) {
-      // residual already in F.res
-    } else if (F.g->plane >= mg->engine_min_plane) {
-      PB_TRY(ghosts(F, F.x, &lo, &hi));
-      PB_TRY(launch_mg_residual(F.g, F.s, F.x, F.b, StencilPlanes{lo, hi}, F.res, mg->skip));
-    } else {
-      PB_TRY(ghosts(F, F.x, &lo, &hi));
-      hipLaunchKernelGGL(mg_residual_kernel, dim3(mg_blocks(ctx, G.nlocal / 2)), dim3(256), 0,
-                         ctx->stream, G, (const double*)F.x, (const double*)F.b, lo, hi, F.s,
-                         F.res, mg->skip);
-      PB_HIP(hipGetLastError());
-    }
-    PB_TRY(ghosts(F, F.res, &lo, &hi));
-    const MgGeo CG = Cl.geo();
-    const int64_t cols = (int64_t)CG.nx * CG.ny;
-    if (cols >= mg->restrict_z_min_cols) {
-      int64_t nchunk = 1;
-      const int kc = transfer_chunk(ctx, cols, CG.nzl, &nchunk);
-      hipLaunchKernelGGL(mg_restrict_z_kernel, dim3(mg_blocks(ctx, cols * nchunk)), dim3(256), 0,
-                         ctx->stream, G, (const double*)F.res, lo, hi, CG, kc, Cl.b, mg->skip);
-    } else {
-      hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_blocks(ctx, CG.nlocal)), dim3(256), 0,
-                         ctx->stream, G, (const double*)F.res, lo, hi, CG, Cl.b, mg->skip);
-    }
-    PB_HIP(hipGetLastError());
-  }
-  const bool agg = mg->La > 0;
-  if (agg) {  // gather level La's right-hand side onto every rank (P copies out, P slabs in)
-    ScopedTimer tg(ctx, "mg_coarse_levels");
-    const MgLevel& A0 = mg->lv[mg->La];
-    const size_t bytes = (size_t)A0.g->nlocal * sizeof(double);
-    for (int r = 0; r < ctx->nranks; ++r)
-      PB_HIP(hipMemcpyAsync(mg->agg_send + (int64_t)r * A0.g->nlocal, A0.b, bytes,
-                            hipMemcpyDeviceToDevice, ctx->stream));
-    PB_TRY(alltoallv_device(ctx, mg->agg_send, mg->agg_sc.data(), mg->ab[0], mg->agg_rc.data()));
-  }
-  if (Lt < L) {
-    ScopedTimer t3(ctx, "mg_coarse_levels");
-    TailArgs A{};
-    A.nl = L - Lt;
-    A.coarse_its = mg->coarse_its;
-    A.omega = mg->omega;
-    int64_t off = 0;
-    for (int t = 0; t < A.nl; ++t) {
-      const MgLevel& lv = mg->lv[Lt + t];
-      A.lv[t] = agg ? TailLevel{mg->ageo[t], mg->ax[t], mg->ab[t], mg->ares[t], lv.s, 0, 0, 0}
-                    : TailLevel{lv.geo(), lv.x, lv.b, lv.res, lv.s, 0, 0, 0};
-      const int64_t n = ((agg ? mg->ageo[t].nlocal : lv.g->nlocal) + 1) & ~(int64_t)1;  // 16-byte aligned arrays
-      A.lv[t].ox = off;
-      A.lv[t].ob = off + n;
-      A.lv[t].ores = off + 2 * n;
-      off += (t + 1 < A.nl ? 3 : 2) * n;
-    }
-    // the tail in LDS when it fits (512^3: 109 KB of the 160 KB per CU)
-    const size_t lds = (size_t)off * sizeof(double);
-    A.lds = lds <= kTailLdsMax;
-    if (A.lds && !mg->tail_attr) {
-      PB_HIP(hipFuncSetAttribute((const void*)mg_tail_kernel,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailLdsMax));
-      mg->tail_attr = true;
-    }
-    hipLaunchKernelGGL(mg_tail_kernel, dim3(1), dim3(512), A.lds ? lds : 0, ctx->stream, A,
-                       mg->skip);
-    PB_HIP(hipGetLastError());
-  } else {
-    ScopedTimer t3(ctx, L > 1 ? "mg_coarse_levels" : "mg_fine_smooth_first");
-    PB_TRY(coarse_solve(mg, mg->lv[L - 1], L == 1 ? sums_st : nullptr, nparts));
-  }
-  // up: prolongate + correct, post-smooth; with a tail, the first host up-leg prolongates from Lt
-  for (int l = Lt < L ? Lt - 1 : L - 2; l >= 0; --l) {
-    MgLevel& F = mg->lv[l];
-    MgLevel& Cl = mg->lv[l + 1];
-    ScopedTimer t4(ctx, l == 0 ? "mg_fine_prolong_post" : "mg_coarse_levels");
-    if (post_fused(mg, l)) {
-      // prolongation + correction + both post-smoothing half-sweeps in one pass, xs -> x
-      // (agglomerated coarse level: this rank's planes of the full coarse correction)
-      const bool from_agg = agg && l + 1 == mg->La;
-      const double* xcp = from_agg ? mg->ax[0] + Cl.g->k0 * Cl.g->plane : Cl.x;
-      PB_TRY(launch_post_sweep(F.g, F.s, Cl.g, F.xs, xcp, F.b, F.x, mg->omega, mg->skip,
-                               l == 0 ? sums_st : nullptr, l == 0 ? nparts : nullptr,
-                               from_agg ? mg->ax[0] : nullptr));
-      continue;
-    }
-    const double *lo, *hi;
-    const double* xc = Cl.x;
-    if (agg && l + 1 == mg->La) {  // this rank's planes of the full coarse correction
-      const int64_t pc = Cl.g->plane, nzc = Cl.n[2], k0c = Cl.g->k0, nzl = Cl.g->nzl;
-      xc = mg->ax[0] + k0c * pc;
-      lo = mg->ax[0] + ((k0c - 1 + nzc) % nzc) * pc;
-      hi = mg->ax[0] + ((k0c + nzl) % nzc) * pc;
-    } else {
-      PB_TRY(ghosts(Cl, Cl.x, &lo, &hi));
-    }
-    const MgGeo G = F.geo(), CG = Cl.geo();
-    const int64_t cols = (int64_t)CG.nx * CG.ny;
-    bool fused = false;
-    if (cols >= mg->restrict_z_min_cols) {
-      int64_t nchunk = 1;
-      const int kc = transfer_chunk(ctx, cols, CG.nzl, &nchunk);
-      // fused post-smoothing: prolongate into the residual scratch, then both half-sweeps in one
-      // pass back into F.x (which also takes CG's residual sums on level 0)
-      fused = F.res && F.g->plane >= mg->engine_min_plane && sor_sweep2_supported(F.g);
-      hipLaunchKernelGGL(mg_prolong_z_kernel, dim3(mg_blocks(ctx, cols * nchunk)), dim3(256), 0,
-                         ctx->stream, G, (const double*)F.x, fused ? F.res : F.x, CG, kc, xc, lo,
-                         hi, mg->skip);
-    } else {
-      hipLaunchKernelGGL(mg_prolong_cell_kernel, dim3(mg_blocks(ctx, CG.nlocal)), dim3(256), 0,
-                         ctx->stream, G, F.x, CG, xc, lo, hi, mg->skip);
-    }
-    PB_HIP(hipGetLastError());
-    if (fused) {
-      PB_TRY(launch_sor_sweep2(F.g, F.s, F.res, F.b, F.x, mg->omega, 1, mg->skip,
-                               l == 0 ? sums_st : nullptr, l == 0 ? nparts : nullptr));
-    } else {
-      PB_TRY(smooth(mg, F, 1, 0));
-      PB_TRY(smooth(mg, F, 0, 0, l == 0 ? sums_st : nullptr, nparts));
-    }
-  }
-  return PB_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Selectable level smoothers (pb_pc_mg_opts): the V-cycle by per-level launches
-// ---------------------------------------------------------------------------------------------
-int mg_set_smoother(Mg* mg, const MgSmoother& sm) {
-  const int L = (int)mg->lv.size();
-  if (sm.pc == PB_MG_LEVELS_JACOBI && !mg->pmem && L > 1) {
-    int64_t total = 0;
-    for (int l = 0; l < L - 1; ++l) total += 3 * mg->lv[l].g->nlocal;
-    if (hipMalloc(&mg->pmem, (size_t)total * sizeof(double)) != hipSuccess)
-      return set_error(PB_ERR_ALLOC, "multigrid level smoother: out of device memory");
-    double* p = mg->pmem;
-    for (int l = 0; l < L - 1; ++l) {
-      MgLevel& lv = mg->lv[l];
-      lv.t1 = p;
-      lv.t2 = p + lv.g->nlocal;
-      lv.r2 = p + 2 * lv.g->nlocal;
-      p += 3 * lv.g->nlocal;
-    }
-  }
-  mg->sm = sm;
-  return PB_OK;
-}
-
-// res = b - A x of level F (engine on large levels, the pair kernel below)
-static int level_residual(Mg* mg, MgLevel& F, const double* x, double* res) {
+int level_residual(Mg* mg, MgLevel& F, const double* x, double* res) {
   const double *lo, *hi;
   PB_TRY(ghosts(F, x, &lo, &hi));
-  if (F.g->plane >= mg->engine_min_plane)
+  if (F.plan.engine)
     return launch_mg_residual(F.g, F.s, x, F.b, StencilPlanes{lo, hi}, res, mg->skip);
   const MgGeo G = F.geo();
-  hipLaunchKernelGGL(mg_residual_kernel, dim3(mg_blocks(mg->ctx, G.nlocal / 2)), dim3(256), 0,
+  hipLaunchKernelGGL(mg_residual_kernel, dim3(mg_blocks(G.nlocal / 2)), dim3(256), 0,
                      mg->ctx->stream, G, x, (const double*)F.b, lo, hi, F.s, res, mg->skip);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-static int level_restrict(Mg* mg, MgLevel& F, const double* res, MgLevel& Cl) {
+int level_restrict(Mg* mg, MgLevel& F, const double* res, MgLevel& C) {
   const double *lo, *hi;
   PB_TRY(ghosts(F, res, &lo, &hi));
-  const MgGeo G = F.geo(), CG = Cl.geo();
-  const int64_t cols = (int64_t)CG.nx * CG.ny;
-  if (cols >= mg->restrict_z_min_cols) {
+  const MgGeo G = F.geo(), CG = C.geo();
+  if (F.plan.march) {
+    const int64_t cols = (int64_t)CG.nx * CG.ny;
     int64_t nchunk = 1;
     const int kc = transfer_chunk(mg->ctx, cols, CG.nzl, &nchunk);
-    hipLaunchKernelGGL(mg_restrict_z_kernel, dim3(mg_blocks(mg->ctx, cols * nchunk)), dim3(256), 0,
-                       mg->ctx->stream, G, res, lo, hi, CG, kc, Cl.b, mg->skip);
+    hipLaunchKernelGGL(mg_restrict_z_kernel, dim3(mg_blocks(cols * nchunk)), dim3(256), 0,
+                       mg->ctx->stream, G, res, lo, hi, CG, kc, C.b, mg->skip);
   } else {
-    hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_blocks(mg->ctx, CG.nlocal)), dim3(256), 0,
-                       mg->ctx->stream, G, res, lo, hi, CG, Cl.b, mg->skip);
+    hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_blocks(CG.nlocal)), dim3(256), 0,
+                       mg->ctx->stream, G, res, lo, hi, CG, C.b, mg->skip);
   }
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-// xf += P xc, in place
-static int level_prolong(Mg* mg, MgLevel& F, double* xf, MgLevel& Cl) {
-  const double *lo, *hi;
-  PB_TRY(ghosts(Cl, Cl.x, &lo, &hi));
-  const MgGeo G = F.geo(), CG = Cl.geo();
-  const int64_t cols = (int64_t)CG.nx * CG.ny;
-  if (cols >= mg->restrict_z_min_cols) {
+int level_prolong(Mg* mg, MgLevel& F, const double* xf, double* xout, MgLevel& C,
+                  const CoarsePlanes* cp) {
+  CoarsePlanes p{C.x, nullptr, nullptr};
+  if (cp) p = *cp;
+  else PB_TRY(ghosts(C, C.x, &p.lo, &p.hi));
+  const MgGeo G = F.geo(), CG = C.geo();
+  if (F.plan.march) {
+    const int64_t cols = (int64_t)CG.nx * CG.ny;
     int64_t nchunk = 1;
     const int kc = transfer_chunk(mg->ctx, cols, CG.nzl, &nchunk);
-    hipLaunchKernelGGL(mg_prolong_z_kernel, dim3(mg_blocks(mg->ctx, cols * nchunk)), dim3(256), 0,
-                       mg->ctx->stream, G, (const double*)xf, xf, CG, kc, (const double*)Cl.x, lo,
-                       hi, mg->skip);
+    hipLaunchKernelGGL(mg_prolong_z_kernel, dim3(mg_blocks(cols * nchunk)), dim3(256), 0,
+                       mg->ctx->stream, G, xf, xout, CG, kc, p.xc, p.lo, p.hi, mg->skip);
   } else {
-    hipLaunchKernelGGL(mg_prolong_cell_kernel, dim3(mg_blocks(mg->ctx, CG.nlocal)), dim3(256), 0,
-                       mg->ctx->stream, G, xf, CG, (const double*)Cl.x, lo, hi, mg->skip);
+    if (xout != xf) return set_error(PB_ERR_ARG, "the per-cell prolongation runs in place");
+    hipLaunchKernelGGL(mg_prolong_cell_kernel, dim3(mg_blocks(CG.nlocal)), dim3(256), 0,
+                       mg->ctx->stream, G, xout, CG, p.xc, p.lo, p.hi, mg->skip);
   }
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-// One step of a Jacobi-type smoother on level F. y == nullptr: the zero start (r = b);
-// yp == nullptr: no y_prev term. r_out == nullptr: the iterate alone (y_out may alias an input).
+// f(N) with N = std::integral_constant<int, n>, n = 1 | 2 | 3: a polynomial kernel's inputs
+template <class Fn>
+static void with_poly_inputs(int n, Fn&& f) {
+  if (n == 1) f(std::integral_constant<int, 1>{});
+  else if (n == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 3>{});
+}
+
 // Fused (one rank, tuning mg_poly_fused = 1): the engine pass on large levels, the pair kernel
 // below; else the vector kernel, a ghost exchange of y_out and the residual pass -- the same
 // expressions, so the same bits, and what a decomposed grid runs.
-static int poly_step(Mg* mg, MgLevel& F, const double* y, const double* yp, const double* r,
-                     double scale, double omega, double* y_out, double* r_out) {
+int poly_step(Mg* mg, MgLevel& F, const double* y, const double* yp, const double* r, double scale,
+              double omega, double* y_out, double* r_out) {
   pb_ctx* ctx = mg->ctx;
   const MgGeo G = F.geo();
   const int n = !y ? 1 : (!yp ? 2 : 3);
@@ -1184,124 +732,56 @@ static int poly_step(Mg* mg, MgLevel& F, const double* y, const double* yp, cons
   const PolyArgs A = n == 1 ? PolyArgs{F.b, nullptr, nullptr, scale, omega, dinv}
                    : n == 2 ? PolyArgs{y, r, nullptr, scale, omega, dinv}
                             : PolyArgs{y, yp, r, scale, omega, dinv};
-  const dim3 grid(mg_blocks(ctx, G.nlocal / 2)), block(256);
-  const bool fused = r_out && !ctx->split && tune("mg_poly_fused", 1) != 0;
-  if (fused && F.g->plane >= mg->engine_min_plane)
+  const dim3 grid(mg_blocks(G.nlocal / 2)), block(256);
+  const bool fused = r_out && !ctx->split && mg->tn.poly_fused;
+  if (fused && F.plan.engine)
     return launch_mg_poly(F.g, F.s, y, yp, r, F.b, scale, omega, y_out, r_out, mg->skip);
   if (fused) {
     const double* b = F.b;
-    if (n == 1)
-      hipLaunchKernelGGL(mg_poly_kernel<1>, grid, block, 0, ctx->stream, G, A, b, F.s, y_out, r_out,
-                         mg->skip);
-    else if (n == 2)
-      hipLaunchKernelGGL(mg_poly_kernel<2>, grid, block, 0, ctx->stream, G, A, b, F.s, y_out, r_out,
-                         mg->skip);
-    else
-      hipLaunchKernelGGL(mg_poly_kernel<3>, grid, block, 0, ctx->stream, G, A, b, F.s, y_out, r_out,
-                         mg->skip);
+    with_poly_inputs(n, [&](auto N) {
+      hipLaunchKernelGGL(mg_poly_kernel<decltype(N)::value>, grid, block, 0, ctx->stream, G, A, b,
+                         F.s, y_out, r_out, mg->skip);
+    });
     PB_HIP(hipGetLastError());
     return PB_OK;
   }
   const int64_t npairs = G.nlocal / 2;
-  if (n == 1)
-    hipLaunchKernelGGL(mg_poly_x_kernel<1>, grid, block, 0, ctx->stream, npairs, A, y_out, mg->skip);
-  else if (n == 2)
-    hipLaunchKernelGGL(mg_poly_x_kernel<2>, grid, block, 0, ctx->stream, npairs, A, y_out, mg->skip);
-  else
-    hipLaunchKernelGGL(mg_poly_x_kernel<3>, grid, block, 0, ctx->stream, npairs, A, y_out, mg->skip);
+  with_poly_inputs(n, [&](auto N) {
+    hipLaunchKernelGGL(mg_poly_x_kernel<decltype(N)::value>, grid, block, 0, ctx->stream, npairs,
+                       A, y_out, mg->skip);
+  });
   PB_HIP(hipGetLastError());
   return r_out ? level_residual(mg, F, y_out, r_out) : PB_OK;
 }
 
-// nu steps of the Jacobi-type smoother on level F. pre: from zero, every step with its residual
-// (the last one's is the V-cycle's); *ycur, *rcur = where the iterate and its residual ended up.
-// post: from *ycur (its residual taken first), the last step stores no residual and writes F.x.
-static int poly_smooth(Mg* mg, MgLevel& F, bool pre, double** ycur, double** rcur) {
-  const MgSmoother& sm = mg->sm;
-  const bool cheb = sm.ksp == PB_MG_LEVELS_CHEBYSHEV;
-  double scale = sm.rich_scale, mu = 0.0, omegaprod = 0.0, rho = 0.0;
-  if (cheb) {  // KSPSolve_Chebyshev's coefficients, restarted at every smoothing call
-    scale = 2.0 / (sm.emax + sm.emin);
-    const double alpha = 1.0 - scale * sm.emin;
-    mu = 1.0 / alpha;
-    omegaprod = 2.0 / alpha;
-    rho = 1.0 / mu;
+int launch_tail(Mg* mg, int Lt, bool agg) {
+  pb_ctx* ctx = mg->ctx;
+  TailArgs A{};
+  A.nl = (int)mg->lv.size() - Lt;
+  A.coarse_its = mg->coarse_its;
+  A.omega = mg->omega;
+  int64_t off = 0;
+  for (int t = 0; t < A.nl; ++t) {
+    const MgLevel& lv = mg->lv[Lt + t];
+    A.lv[t] = agg ? TailLevel{mg->ageo[t], mg->ax[t], mg->ab[t], mg->ares[t], lv.s, 0, 0, 0}
+                  : TailLevel{lv.geo(), lv.x, lv.b, lv.res, lv.s, 0, 0, 0};
+    const int64_t n = (A.lv[t].G.nlocal + 1) & ~(int64_t)1;  // 16-byte aligned arrays
+    A.lv[t].ox = off;
+    A.lv[t].ob = off + n;
+    A.lv[t].ores = off + 2 * n;
+    off += (t + 1 < A.nl ? 3 : 2) * n;
   }
-  double* const ybuf[3] = {F.x, F.t1, F.t2};
-  auto pick = [&](const double* a, const double* c) {
-    for (double* q : ybuf)
-      if (q != a && q != c) return q;
-    return (double*)nullptr;
-  };
-  const double* y = nullptr;
-  const double* yp = nullptr;
-  const double* r = nullptr;
-  if (!pre) {
-    y = *ycur;
-    PB_TRY(level_residual(mg, F, y, F.res));
-    r = F.res;
+  // the tail in LDS when it fits (512^3: 109 KB of the 160 KB per CU)
+  const size_t lds = (size_t)off * sizeof(double);
+  A.lds = lds <= kTailLdsMax;
+  if (A.lds && !mg->tail_attr) {
+    PB_HIP(hipFuncSetAttribute((const void*)mg_tail_kernel,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailLdsMax));
+    mg->tail_attr = true;
   }
-  for (int i = 0; i < sm.nu; ++i) {
-    double omega = 1.0;
-    if (cheb && i >= 1) {
-      rho = 1.0 / (2.0 * mu - rho);
-      omega = omegaprod * rho;
-    }
-    // y_prev enters from Chebyshev's second step on; after a zero start it is 0 in step 1
-    const double* ypa = cheb && i >= 1 && !(pre && i == 1) ? yp : nullptr;
-    const bool last = !pre && i == sm.nu - 1;
-    double* yo = last ? F.x : pick(y, yp);
-    double* ro = last ? nullptr : (r == F.res ? F.r2 : F.res);
-    PB_TRY(poly_step(mg, F, y, ypa, r, scale, omega, yo, ro));
-    yp = y;
-    y = yo;
-    r = ro;
-  }
-  *ycur = const_cast<double*>(y);
-  *rcur = const_cast<double*>(r);
-  return PB_OK;
-}
-
-static int mg_apply_levels(Mg* mg, const double* r, double* z, const int* skip) {
-  ScopedTimer tm(mg->ctx, "mg_apply");
-  mg->skip = skip;
-  mg->engine_min_plane = tune("mg_engine_min_plane", mg_engine_min_plane_default(mg->ctx));
-  mg->restrict_z_min_cols = tune("mg_restrict_z_min_cols", 4096);
-  const int L = (int)mg->lv.size();
-  const int nu = mg->sm.nu;
-  mg->lv[0].b = const_cast<double*>(r);
-  mg->lv[0].x = z;
-  std::vector<double*> cur(L, nullptr);  // where level l's pre-smoothed iterate lives
-  for (int l = 0; l < L - 1; ++l) {  // down: pre-smooth, residual, restrict
-    MgLevel& F = mg->lv[l];
-    double* res = F.res;
-    if (mg->poly()) {
-      PB_TRY(poly_smooth(mg, F, true, &cur[l], &res));
-    } else {  // nu x (red, black), the first pair from zero
-      PB_TRY(smooth(mg, F, 0, 1));
-      for (int i = 1; i < nu; ++i) {
-        PB_TRY(smooth(mg, F, 0, 0));
-        PB_TRY(smooth(mg, F, 1, 0));
-      }
-      cur[l] = F.x;
-      PB_TRY(level_residual(mg, F, F.x, res));
-    }
-    PB_TRY(level_restrict(mg, F, res, mg->lv[l + 1]));
-  }
-  PB_TRY(coarse_solve(mg, mg->lv[L - 1], nullptr, nullptr));
-  for (int l = L - 2; l >= 0; --l) {  // up: prolongate + correct, post-smooth
-    MgLevel& F = mg->lv[l];
-    PB_TRY(level_prolong(mg, F, cur[l], mg->lv[l + 1]));
-    if (mg->poly()) {
-      double* res = nullptr;
-      PB_TRY(poly_smooth(mg, F, false, &cur[l], &res));
-    } else {  // nu x (black, red): the pre-smoothing mirrored
-      for (int i = 0; i < nu; ++i) {
-        PB_TRY(smooth(mg, F, 1, 0));
-        PB_TRY(smooth(mg, F, 0, 0));
-      }
-    }
-  }
+  hipLaunchKernelGGL(mg_tail_kernel, dim3(1), dim3(512), A.lds ? lds : 0, ctx->stream, A,
+                     mg->skip);
+  PB_HIP(hipGetLastError());
   return PB_OK;
 }
 

@@ -1121,6 +1121,15 @@ static int sweep2_ghosts(pb_grid* g, const double* xin, const double* b, Sweep2G
   return PB_OK;
 }
 
+// nchunk z-chunks of a multiple of `align` planes (the kernels' chunk-start parity); returns the
+// workgroup count
+static int64_t set_chunks(Sweep2Geo& geo, int nchunk, int align) {
+  geo.kc = (geo.nzl + nchunk - 1) / nchunk;
+  geo.kc = (geo.kc + align - 1) / align * align;
+  geo.nchunk = (geo.nzl + geo.kc - 1) / geo.kc;
+  return (int64_t)geo.nseg * geo.ntile * geo.nchunk;
+}
+
 static int64_t sweep2_geo(pb_grid* g, Sweep2Geo& geo) {
   geo.nx = (int)g->n[0];
   geo.ny = (int)g->n[1];
@@ -1137,9 +1146,21 @@ static int64_t sweep2_geo(pb_grid* g, Sweep2Geo& geo) {
   const int target = 16 * g->ctx->num_cus;
   int nchunk = std::max(1, (target + columns - 1) / columns);
   nchunk = std::min(nchunk, std::max(1, geo.nzl / 16));
-  geo.kc = (geo.nzl + nchunk - 1) / nchunk;
-  geo.nchunk = (geo.nzl + geo.kc - 1) / geo.kc;
-  return (int64_t)columns * geo.nchunk;
+  return set_chunks(geo, nchunk, 1);
+}
+
+// CG's residual sums of a fused sweep's output: a partial of four per workgroup into
+// ctx->d_partials, *nparts = their count. Null where no sums are asked for
+static int sums_parts(const pb_grid* g, const CgState* sums_st, int64_t nblocks, int* nparts,
+                      double** parts) {
+  *parts = nullptr;
+  if (!sums_st) return PB_OK;
+  if (nblocks * 4 > g->ctx->partials_cap)
+    return set_error(PB_ERR_UNSUPPORTED, "fused sweep of %lld blocks exceeds partials capacity",
+                     (long long)nblocks);
+  *parts = g->ctx->d_partials;
+  if (nparts) *nparts = (int)nblocks;
+  return PB_OK;
 }
 
 int launch_sor_sweep2(pb_grid* g, const Star& s, const double* xin, const double* b, double* xout,
@@ -1149,21 +1170,13 @@ int launch_sor_sweep2(pb_grid* g, const Star& s, const double* xin, const double
   Sweep2Geo geo;
   const int64_t nblocks = sweep2_geo(g, geo);
   PB_TRY(sweep2_ghosts(g, xin, b, geo));
-  if (sums_st) {
-    if (nblocks * 4 > g->ctx->partials_cap)
-      return set_error(PB_ERR_UNSUPPORTED, "fused sweep of %lld blocks exceeds partials capacity",
-                       (long long)nblocks);
-    auto kern = geo.split ? sor_sweep2_kernel<true, true> : sor_sweep2_kernel<true, false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(kThreads), 0,
-                       g->ctx->stream, geo, s.cx, s.cy, s.cz, s.cc, omega, c1, xin, b, xout,
-                       sums_st, g->ctx->d_partials, skip);
-    if (nparts) *nparts = (int)nblocks;
-  } else {
-    auto kern = geo.split ? sor_sweep2_kernel<false, true> : sor_sweep2_kernel<false, false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(kThreads), 0,
-                       g->ctx->stream, geo, s.cx, s.cy, s.cz, s.cc, omega, c1, xin, b, xout,
-                       (const CgState*)nullptr, (double*)nullptr, skip);
-  }
+  double* parts;
+  PB_TRY(sums_parts(g, sums_st, nblocks, nparts, &parts));
+  auto kern = sums_st ? (geo.split ? sor_sweep2_kernel<true, true> : sor_sweep2_kernel<true, false>)
+                      : (geo.split ? sor_sweep2_kernel<false, true>
+                                   : sor_sweep2_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(kThreads), 0, g->ctx->stream, geo, s.cx,
+                     s.cy, s.cz, s.cc, omega, c1, xin, b, xout, sums_st, parts, skip);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
@@ -1183,6 +1196,24 @@ static int64_t balanced_split(const pb_grid* g, Sweep2Geo& geo, int per_cu, int 
   return T * ncol + (ncol * h + w - 1) / w;
 }
 
+// The u4 passes' common setup. What the level's plan (level_plan, pb_mg.cpp) guarantees is checked
+// once more for a caller that did not ask it -- a coarse grid of half the extents, on N ranks
+// slabs of min_planes planes for the ghosts (else the error `thin`) and an even slab origin -- then
+// sweep2_geo's geometry with tiles of `rows` stored rows and no ghost planes yet
+static int u4_setup(const char* what, pb_grid* g, const pb_grid* cg, int min_planes,
+                    const char* thin, int rows, Sweep2Geo& geo) {
+  if (cg->n[0] * 2 != g->n[0] || cg->n[1] * 2 != g->n[1] || cg->nzl * 2 != g->nzl)
+    return set_error(PB_ERR_ARG, "%s: coarse grid is not half the fine one", what);
+  if (g->ctx->split && (g->nzl < min_planes || cg->nzl < 2))
+    return set_error(PB_ERR_UNSUPPORTED, "%s", thin);
+  if (g->k0 % 2 != 0) return set_error(PB_ERR_UNSUPPORTED, "%s: odd slab origin", what);
+  sweep2_geo(g, geo);
+  geo.split = 0;
+  geo.xg = geo.bg_lo = geo.bg_hi = nullptr;
+  geo.ntile = (geo.ny + rows - 1) / rows;
+  return PB_OK;
+}
+
 int launch_post_sweep(pb_grid* g, const Star& s, const pb_grid* cg, const double* xs,
                       const double* xc, const double* b, double* xout, double omega,
                       const int* skip, const CgState* sums_st, int* nparts,
@@ -1190,18 +1221,16 @@ int launch_post_sweep(pb_grid* g, const Star& s, const pb_grid* cg, const double
   ScopedTimer tm(g->ctx, "mg_post_sweep");
   const bool split = g->ctx->split;
   if (xs == xout) return set_error(PB_ERR_ARG, "fused post-smoothing must run out of place");
-  if (cg->n[0] * 2 != g->n[0] || cg->n[1] * 2 != g->n[1] || cg->nzl * 2 != g->nzl)
-    return set_error(PB_ERR_ARG, "fused post-smoothing: coarse grid is not half the fine one");
+  // 8 waves x 4 rows (unrolled: compile-time colours need an even k0, chunks start at multiples
+  // of 4)
+  constexpr int nw = 8, ty = 4;
   Sweep2Geo geo;
-  int64_t nblocks = sweep2_geo(g, geo);
-  geo.split = 0;
-  geo.xg = geo.bg_lo = geo.bg_hi = nullptr;
+  PB_TRY(u4_setup("fused post-smoothing", g, cg, 2, "fused post-smoothing: slabs of < 2 planes",
+                  nw * ty - 4, geo));
   PostGeo cgeo{(int)cg->n[0], (int)cg->n[1], (int)cg->nzl, cg->plane, 0,
                 {nullptr, nullptr, nullptr, nullptr}};
   if (split) {  // x_s two deep, b one deep, the coarse correction two deep
     pb_grid* gc = const_cast<pb_grid*>(cg);
-    if (g->nzl < 2 || gc->nzl < 2)
-      return set_error(PB_ERR_UNSUPPORTED, "fused post-smoothing: slabs of < 2 planes");
     PB_TRY(ensure_ghost2(g));
     PB_TRY(ensure_ghost2(gc));
     PB_TRY(halo_exchange_n(g, xs, xs + (g->nzl - 2) * g->plane, 2, g->ghost2,
@@ -1226,10 +1255,6 @@ int launch_post_sweep(pb_grid* g, const Star& s, const pb_grid* cg, const double
       for (int i = 0; i < 4; ++i) cgeo.cgh[i] = gc->ghost2 + (int64_t)i * gc->plane;
     }
   }
-  // 8 waves x 4 rows (unrolled: compile-time colours need an even k0, chunks start at multiples
-  // of 4)
-  constexpr int nw = 8, ty = 4;
-  geo.ntile = (geo.ny + nw * ty - 5) / (nw * ty - 4);
   const int columns = geo.nseg * geo.ntile;
   // z-chunks: every chunk re-reads two planes and runs up to five spare ones, so chunks stay
   // >= 64 planes where the grid has 512 (measured: 0.733 -> 0.700 ms at 512^3 against 16) and
@@ -1238,22 +1263,14 @@ int launch_post_sweep(pb_grid* g, const Star& s, const pb_grid* cg, const double
   int nchunk = std::max(1, (target + columns - 1) / columns);
   const int minz = std::min(64, std::max(16, geo.nzl / 8));
   nchunk = std::min(nchunk, std::max(1, geo.nzl / minz));
-  geo.kc = (geo.nzl + nchunk - 1) / nchunk;
-  geo.kc = (geo.kc + 3) & ~3;
-  geo.nchunk = (geo.nzl + geo.kc - 1) / geo.kc;
-  nblocks = (int64_t)columns * geo.nchunk;
-  if (g->k0 % 2 != 0)
-    return set_error(PB_ERR_UNSUPPORTED, "fused post-smoothing: odd slab origin");
+  int64_t nblocks = set_chunks(geo, nchunk, 4);
   // (mg_u4_split: the balanced work split, tests only -- slower here at any count, r04)
   nblocks = balanced_split(g, geo, std::max(0, tune("mg_u4_split", 0)), 4, nblocks);
-  if (sums_st && nblocks * 4 > g->ctx->partials_cap)
-    return set_error(PB_ERR_UNSUPPORTED, "fused sweep of %lld blocks exceeds partials capacity",
-                     (long long)nblocks);
+  double* parts;
+  PB_TRY(sums_parts(g, sums_st, nblocks, nparts, &parts));
   auto kern = sums_st ? post_sweep_u4_kernel<true, nw, ty> : post_sweep_u4_kernel<false, nw, ty>;
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * nw), 0, g->ctx->stream, geo, cgeo,
-                     s.cx, s.cy, s.cz, s.cc, omega, xs, xc, b, xout, sums_st,
-                     sums_st ? g->ctx->d_partials : (double*)nullptr, skip);
-  if (sums_st && nparts) *nparts = (int)nblocks;
+                     s.cx, s.cy, s.cz, s.cc, omega, xs, xc, b, xout, sums_st, parts, skip);
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
@@ -1262,17 +1279,15 @@ int launch_presmooth_restrict(pb_grid* g, const Star& s, const pb_grid* cg, cons
                               double* xout, double* bc, double omega, const int* skip) {
   ScopedTimer tm(g->ctx, "mg_presmooth_restrict");
   const bool split = g->ctx->split;
-  if (split && g->nzl < 3)
-    return set_error(PB_ERR_UNSUPPORTED, "fused restriction on N ranks: >= 3 planes per slab");
   if (b == xout) return set_error(PB_ERR_ARG, "fused pre-smoothing must run out of place");
   if (!sor_sweep2_supported(g) || g->nzl % 2)
     return set_error(PB_ERR_UNSUPPORTED, "fused restriction: grid not supported");
-  if (cg->n[0] * 2 != g->n[0] || cg->n[1] * 2 != g->n[1] || cg->nzl * 2 != g->nzl)
-    return set_error(PB_ERR_ARG, "fused restriction: coarse grid is not half the fine one");
+  // 8 waves x 4 rows, the plane loop unrolled by four (compile-time colours: even k0, even
+  // chunk starts)
+  constexpr int nw = 8, ty = 4;
   Sweep2Geo geo;
-  sweep2_geo(g, geo);
-  geo.split = 0;
-  geo.xg = geo.bg_lo = geo.bg_hi = nullptr;
+  PB_TRY(u4_setup("fused restriction", g, cg, 3,
+                  "fused restriction on N ranks: >= 3 planes per slab", nw * ty - 8, geo));
   if (split) {  // b three deep (planes -3 .. -1 | nzl .. nzl+2)
     PB_TRY(ensure_ghost2(g));
     PB_TRY(halo_exchange_n(g, b, b + (g->nzl - 3) * g->plane, 3, g->ghost2,
@@ -1280,10 +1295,6 @@ int launch_presmooth_restrict(pb_grid* g, const Star& s, const pb_grid* cg, cons
     geo.split = 1;
     geo.xg = g->ghost2;
   }
-  // 8 waves x 4 rows, the plane loop unrolled by four (compile-time colours: even k0, even
-  // chunk starts)
-  constexpr int nw = 8, ty = 4;
-  geo.ntile = (geo.ny + nw * ty - 9) / (nw * ty - 8);
   const int columns = geo.nseg * geo.ntile;
   // z-chunks: each chunk forms red, black and residual values on five planes outside it, and
   // the pass is latency-bound at two waves per SIMD, so (measured at 512^3, one box) few long
@@ -1295,12 +1306,7 @@ int launch_presmooth_restrict(pb_grid* g, const Star& s, const pb_grid* cg, cons
   int nchunk = std::max(1, g->ctx->num_cus / columns);
   if (geo.nzl / nchunk < 128) nchunk = std::max(1, (4 * g->ctx->num_cus + columns - 1) / columns);
   nchunk = std::min(nchunk, std::max(1, geo.nzl / 16));
-  geo.kc = (geo.nzl + nchunk - 1) / nchunk;
-  geo.kc += geo.kc & 1;
-  geo.nchunk = (geo.nzl + geo.kc - 1) / geo.kc;
-  int64_t nblocks = (int64_t)columns * geo.nchunk;
-  if (g->k0 % 2 != 0)
-    return set_error(PB_ERR_UNSUPPORTED, "fused restriction: odd slab origin");
+  int64_t nblocks = set_chunks(geo, nchunk, 2);
   // balanced split (one workgroup per CU where the chunks above need more than one round of
   // workgroups -- this pass runs one per CU (254 VGPRs): 512^3's 256^3 level, 528 workgroups,
   // 0.405 -> 0.382 ms for the coarse levels; on the 512^3 level itself, 220 workgroups in one
