@@ -198,8 +198,29 @@ int pb_vec_device_ptr(pb_vec* v, double** dptr, int64_t* nlocal);
 enum pb_op_kind {
   PB_OP_STAR7 = 0,       /* 2nd-order 7-point star, compute_lapl_pointwise (:84-148)        */
   PB_OP_COMPACT = 1,     /* 6th-order compact lapl = div(grad f), compact_schemes.f90:17-37  */
-  PB_OP_ASSEMBLED27 = 2  /* assembled BOX AIJ P (coefficients.f90:50-113), 27-entry rows     */
+  PB_OP_ASSEMBLED27 = 2, /* assembled BOX AIJ P (coefficients.f90:50-113), 27-entry rows     */
+  PB_OP_VARCOEF = 3      /* 7-point div(beta grad), beta per cell (no reference counterpart:  */
+                         /* what a caller's own MATOP_MULT supplies there, :226-267)          */
 };
+/* PB_OP_VARCOEF: y = div(beta grad x) in flux form, beta cell-centred on the operator's grid, the
+ * face value between two cells their arithmetic or harmonic mean. With c_d = 1 / h_d^2 (the axis
+ * coefficients of pb_lapl_1d_coeffs for the operator's deltas), the neighbours n taken in the
+ * 7-point operator's order without the centre (z-, y-, x-, x+, y+, z+) and every product, sum and
+ * quotient rounded:
+ *   face(a, b) = 0.5 * (a + b)   |   (2.0 * (a * b)) / (a + b)
+ *   g_n = c_d * face(beta_n, beta_c),   t_n = g_n * (x_n - x_c)
+ *   y_c    = ((((t_z- + t_y-) + t_x-) + t_x+) + t_y+) + t_z+
+ *   diag_c = -(((((g_z- + g_y-) + g_x-) + g_x+) + g_y+) + g_z+)
+ * The matrix is symmetric to the bit and constants are in its null space to the bit (KSP's constant
+ * null-space handling applies unchanged). 24 B/DoF per apply: x and beta read, y written; the
+ * operator keeps one field and two ghost planes of beta. A fresh operator has beta = 1, arithmetic.
+ * As A of a KSP it runs every ksp_type through the unfused iterations with any constant-coefficient
+ * P behind every pc_type (the classic pairing: -pc_type mg | fft from a PB_OP_STAR7 P with
+ * representative deltas); as P it supports -pc_type none and jacobi (z = r / diag, the reciprocal
+ * diagonal stored by the KSP and rebuilt after pb_op_set_coefficient / pb_op_set_deltas); sor, mg
+ * and fft from a variable P return PB_ERR_UNSUPPORTED at pb_ksp_create. -ksp_cg_single_reduction
+ * runs the KSPSolve_CG iteration on it. */
+enum pb_coef_mean { PB_COEF_ARITHMETIC = 0, PB_COEF_HARMONIC = 1 };
 /* PB_OP_ASSEMBLED27 applies P x with PETSc's AIJ row sums: stored columns ascending on one rank
  * (MatMult_SeqAIJ), owned columns then off-rank columns on several (MatMult_MPIAIJ) -- so rows on
  * the periodic seams and slab boundaries differ from PB_OP_STAR7 at rounding level, and
@@ -210,7 +231,22 @@ int pb_op_apply(pb_op* op, const pb_vec* x, pb_vec* y); /* ≙ MatMult(A, x, y) 
 /* ≙ assemble_laplacian(da, dx, dy, dz, M) (src/coefficients.f90:50-113): (re)set the spacings
  * the operator's coefficients are built from (lapl_star_coeffs). */
 int pb_op_set_deltas(pb_op* op, const double deltas[3]);
+/* (PB_ERR_UNSUPPORTED on PB_OP_VARCOEF, whose diagonal is a field: pb_op_get_diagonal_vec) */
 int pb_op_get_diagonal(const pb_op* op, double* diag);  /* constant diagonal of the 7-pt P */
+/* Sets the coefficient of a PB_OP_VARCOEF operator (PB_ERR_STATE on another kind, or between
+ * pb_ksp_begin and pb_ksp_end of a KSP that holds the operator). Collective. beta is copied into
+ * storage the operator owns and its two ghost planes are filled by one halo exchange; the caller's
+ * vector is not kept. Every value must be finite and > 0 (a device reduction over all ranks checks
+ * it); PB_ERR_ARG for a value that is not, a vector of another grid or a mean outside
+ * pb_coef_mean. An error leaves the operator as it was. A KSP holding the operator may be reused:
+ * what it derived from the old coefficient is rebuilt by its next solve. */
+int pb_op_set_coefficient(pb_op* op, const pb_vec* beta, int mean);
+/* The coefficient (copied into beta, a vector of the operator's grid) and the mean in force;
+ * either may be NULL. PB_ERR_STATE on another kind. */
+int pb_op_get_coefficient(const pb_op* op, pb_vec* beta, int* mean);
+/* ≙ MatGetDiagonal: diag_c above for PB_OP_VARCOEF, the constant diagonal broadcast for
+ * PB_OP_STAR7 / PB_OP_ASSEMBLED27 (PB_ERR_UNSUPPORTED for PB_OP_COMPACT). */
+int pb_op_get_diagonal_vec(const pb_op* op, pb_vec* diag);
 int pb_op_destroy(pb_op* op);
 /* ≙ MatGetOwnershipRange / VecGetOwnershipRange (src/example.f90:137-147): global row range
  * [first, next) owned by this rank (rank-contiguous natural order of the z-slab split). */

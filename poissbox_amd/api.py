@@ -21,6 +21,10 @@ import numpy as np
 from . import _lib as L
 
 STAR7, COMPACT, ASSEMBLED27 = 0, 1, 2
+# div(beta grad) with beta per cell (Mat.set_coefficient); the face value between two cells is
+# their arithmetic or harmonic mean (pb_coef_mean)
+VARCOEF = 3
+COEF_ARITHMETIC, COEF_HARMONIC = 0, 1
 PC_NONE, PC_JACOBI, PC_SOR, PC_MG, PC_FFT = 0, 1, 2, 3, 4
 # -ksp_type: preonly = one PC application (with -pc_type fft the direct solve), richardson =
 # x += scale M^-1 (b - A x) (ksp_options(richardson_scale=...) or -ksp_richardson_scale)
@@ -375,6 +379,22 @@ class Mat:
     def set_deltas(self, deltas):
         """(Re)set the spacings the coefficients are built from (assemble_laplacian)."""
         L.call("pb_op_set_deltas", self.h, _d_3(deltas))
+
+    def set_coefficient(self, beta, mean=COEF_ARITHMETIC):
+        """VARCOEF: copy the cell-centred coefficient (a Vec of the operator's grid, every value
+        finite and > 0) into the operator; collective."""
+        L.call("pb_op_set_coefficient", self.h, beta.h, int(mean))
+
+    def coefficient(self, beta=None):
+        """VARCOEF: the mean in force; beta (a Vec), if given, receives the coefficient."""
+        m = C.c_int()
+        L.call("pb_op_get_coefficient", self.h, beta.h if beta is not None else None, C.byref(m))
+        return m.value
+
+    def diagonal_vec(self, v):
+        """MatGetDiagonal into the Vec v (VARCOEF: the diagonal field; 7-point kinds: broadcast)."""
+        L.call("pb_op_get_diagonal_vec", self.h, v.h)
+        return v
 
     def destroy(self):
         if self.h:

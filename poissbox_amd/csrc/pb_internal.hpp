@@ -172,6 +172,16 @@ struct pb_op {
   // compact scratch
   double* work = nullptr;
   int64_t work_len = 0;
+  // PB_OP_VARCOEF: the cell-centred coefficient, owned: nzl + 2 planes, beta = local plane 0 and
+  // the planes around it the neighbouring ranks' (one rank: the periodic wrap), filled by
+  // pb_op_set_coefficient; the mean its faces are formed with
+  double* beta_store = nullptr;
+  double* beta = nullptr;
+  int mean = PB_COEF_ARITHMETIC;
+  // counts pb_op_set_coefficient / pb_op_set_deltas: what a KSP derived from the operator (the
+  // variable Jacobi's reciprocal diagonal) is rebuilt by
+  int64_t change = 0;
+  int in_solve = 0;  // KSPs between pb_ksp_begin and pb_ksp_end with this operator as A or P
 };
 
 namespace pb {
@@ -313,6 +323,29 @@ int halo_overlap(pb_grid* g, const double* lo, const double* hi, const StencilPl
 }
 int launch_star7_apply(pb_grid* g, const Star& s, const double* x, double* y,
                        const StencilPlanes& gp, int mode);
+// ---- the variable-coefficient operator (pb_varcoef.hip) ----
+// what a launch reads of a PB_OP_VARCOEF operator: the axis coefficients 1 / h_d^2, beta at local
+// plane 0 (its planes -1 and nzl are the operator's ghost planes) and the mean
+struct VarCoef {
+  double cx, cy, cz;
+  const double* beta;
+  int mean;
+};
+inline VarCoef varcoef_of(const pb_op* op) {
+  return VarCoef{op->cx, op->cy, op->cz, op->beta, op->mean};
+}
+// y = A x over the planes of `mode` (x's planes -1 / nzl by gp); dot: the per-block partial sums
+// of x . y into ctx->d_partials from block part_off on, *nblocks of them (else 0). Honours
+// ctx->op_skip as launch_star7_apply does
+int launch_varcoef_apply(pb_grid* g, const VarCoef& c, const double* x, double* y,
+                         const StencilPlanes& gp, int mode, bool dot, int part_off, int* nblocks);
+// out = diag(A), or its reciprocal (what PCJacobi stores)
+int launch_varcoef_diag(pb_grid* g, const VarCoef& c, double* out, bool recip);
+// *count = the values of v, over all ranks, that are not finite and > 0 (collective, synchronous)
+int varcoef_count_bad(pb_grid* g, const double* v, double* count);
+// z = dinv o r (the Jacobi PC of a variable P); exits at entry when *skip is set
+int launch_varcoef_jacobi(pb_grid* g, const double* dinv, const double* r, double* z,
+                          const int* skip);
 // assembled P (pb_assembled.hip): re-sum the seam and slab-boundary rows of y = P x in PETSc AIJ
 // order after the stencil engine produced y (glo / ghi: x's ghost planes, nullptr on one rank)
 int launch_aij_seams(pb_grid* g, const Star& s, const double* x, const double* glo,
@@ -372,6 +405,9 @@ struct CgState {
   // -ksp_norm_type (pb_ksp_norm_type, never DEFAULT here): the number the stages log and test
   int norm;
 };
+// CgState::pc of the Jacobi PC of a variable-coefficient P: a PC that stores z, like sor / mg / fft
+// (none of pb_pc_type's values; the stages only tell Jacobi / none from the stored-z PCs by it)
+enum { PC_JACOBI_FIELD = 16 };
 // -ksp_norm_type unpreconditioned with a PC that stores z (sor, mg, fft): the
 // pass that forms r leaves partial sums behind sum r^2 in a second region, the upper half of
 // ctx->d_partials (the PC's own four sums fill the lower half after it), and the finalize that

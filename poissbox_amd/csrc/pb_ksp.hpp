@@ -73,6 +73,8 @@ struct pb_ksp {
     int state = 0;
     double emin = 0.0, emax = 0.0, scale = 0.0, mu = 0.0, omegaprod = 0.0;
     double deltas[6] = {0, 0, 0, 0, 0, 0};
+    // ... and for A's and P's change counters then (pb_op_set_coefficient moves them too)
+    int64_t change[2] = {-1, -1};
   };
   Cheb ch;
   // Restarted flexible GMRES (-ksp_type fgmres). v[j] the orthonormal basis,
@@ -116,7 +118,17 @@ struct pb_ksp {
   pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
   int fold_nparts_b = 0;     // partial-sum blocks of the last folded pass B
-  bool stored_z() const { return mg || fft; }  // PCs whose z = M^-1 r is stored (not Jacobi)
+  // -pc_type jacobi from a PB_OP_VARCOEF P: the diagonal is a field, so z = dinv o r is stored like
+  // the PCs' above. dinv = 1.0 / diag(P), built when a solve first needs it and again when P's
+  // change counter has moved on (pb_op_set_coefficient, pb_op_set_deltas)
+  struct VarJacobi {
+    bool on = false;
+    double* dinv = nullptr;
+    int64_t seen = -1;
+  };
+  VarJacobi vj;
+  // PCs whose z = M^-1 r is stored (not the constant-coefficient Jacobi)
+  bool stored_z() const { return mg || fft || vj.on; }
   bool lazy0 = false;  // r0 = b, x0 = 0, p0 = 0 left implicit by pb_ksp_begin
   double* guess_bsums() const { return reinterpret_cast<double*>(d_st + 2); }
   pb::CgState* d_st = nullptr;
@@ -196,8 +208,14 @@ struct OpApplySkip {
   ~OpApplySkip() { ctx->op_skip = nullptr; }
 };
 
+// w = A p inside a CG iteration; *nparts = the blocks of p . w partial sums the operator's own pass
+// left at ctx->d_partials (PB_OP_VARCOEF with tuning varcoef_dot_fused), 0: the caller takes them
+int op_apply_dot(pb_op* op, const double* p, double* w, int* nparts);
+
 // ---- pb_solver.cpp: the driver ----
 int ensure_done_cap(pb_ksp* k, int64_t need);
+// z = M^-1 r of a stored-z preconditioner, nothing else (no sums, no null-space shift)
+int pc_stored_apply(pb_ksp* k, const double* r, double* z, const int* skip = nullptr);
 // z = M^-1 r for the stored-z preconditioners; *np = residual-sum partial blocks written by the
 // PC itself (MG's last sweep), 0 if the caller must take the sums
 int pc_apply_dev(pb_ksp* k, const double* r, double* z, const int* skip, int* np);

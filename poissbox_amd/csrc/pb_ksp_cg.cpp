@@ -174,10 +174,11 @@ static int enqueue_generic_iteration(pb_ksp* k) {
   int np = 0;
   PB_TRY(launch_cg_generic_p(g, k->r, p, k->d_st));
   {
+    // (the variable-coefficient operator may take p . w in its own pass: tuning varcoef_dot_fused)
     OpApplySkip guard(ctx, &k->d_st->done);
-    PB_TRY(op_apply_raw(k->A, p, k->w));
+    PB_TRY(op_apply_dot(k->A, p, k->w, &np));
   }
-  PB_TRY(launch_cg_generic_dot(g, p, k->w, k->d_st, &np));
+  if (np == 0) PB_TRY(launch_cg_generic_dot(g, p, k->w, k->d_st, &np));
   PB_TRY(cg_finalize_pass_a(ctx, np, k->d_st));
   PB_TRY(launch_cg_generic_xr(g, p, k->w, k->x->d, k->r, k->d_st, &np));
   return cg_finalize_stage2(ctx, np, k->log(), k->host_iter);
@@ -224,9 +225,9 @@ static int enqueue_pc_iteration(pb_ksp* k) {
     PB_TRY(launch_cg_generic_p(g, k->z, p, k->d_st, first));  // dinv = 1: z - mu
     {
       OpApplySkip guard(ctx, &k->d_st->done);
-      PB_TRY(op_apply_raw(k->A, p, k->w));
+      PB_TRY(op_apply_dot(k->A, p, k->w, &np));
     }
-    PB_TRY(launch_cg_generic_dot(g, p, k->w, k->d_st, &np));
+    if (np == 0) PB_TRY(launch_cg_generic_dot(g, p, k->w, k->d_st, &np));
   }
   PB_TRY(cg_finalize_pass_a(ctx, np, k->d_st));
   const double* r_in = first ? k->b->d : k->r;

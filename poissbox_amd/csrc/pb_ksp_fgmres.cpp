@@ -175,8 +175,7 @@ int pb::enqueue_fgmres_iteration(pb_ksp* k) {
     PB_TRY(launch_fg_scale(ctx, wt, v, fs, st, n));
     // z_k = N(M^-1 v_k), stored
     if (k->stored_z()) {
-      if (k->fft) PB_TRY(fftpc_apply(k->fft, v, z, &st->done));
-      else PB_TRY(mg_apply(k->mg, v, z, &st->done));
+      PB_TRY(pc_stored_apply(k, v, z, &st->done));
       if (ns) {
         PB_TRY(launch_fg_zsum(ctx, z, fs, st, n));
         PB_TRY(launch_fg_shift(ctx, z, fs, st, n));

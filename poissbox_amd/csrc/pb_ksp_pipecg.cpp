@@ -63,8 +63,7 @@ static int pcg_pc(pb_ksp* k, const double* src, double* dst, const double* sum, 
   PcgState* ps = k->pcg.d;
   if (k->stored_z()) {
     const int* sk = skip ? &st->done : nullptr;
-    if (k->fft) PB_TRY(fftpc_apply(k->fft, src, dst, sk));
-    else PB_TRY(mg_apply(k->mg, src, dst, sk));
+    PB_TRY(pc_stored_apply(k, src, dst, sk));
     if (!ns) return PB_OK;
     // (dinv = 1 with these PCs: dst = dst + (-(sum dst / ntot)), MatNullSpaceRemove's VecShift)
     PB_TRY(launch_pcg_sum(ctx, dst, &ps->zsum, st, skip, n));

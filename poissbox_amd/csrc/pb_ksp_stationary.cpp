@@ -62,10 +62,8 @@ static int rich_pc(pb_ksp* k, const double* r, const int* skip, int* np) {
 static int cheb_pc_n(pb_ksp* k, const double* r, double* z) {
   pb_grid* g = k->A->grid;
   pb_ctx* ctx = g->ctx;
-  if (k->mg) {
-    PB_TRY(mg_apply(k->mg, r, z));
-  } else if (k->fft) {
-    PB_TRY(fftpc_apply(k->fft, r, z));
+  if (k->stored_z()) {
+    PB_TRY(pc_stored_apply(k, r, z));
   } else {
     PB_HIP(hipMemcpyAsync(z, r, (size_t)g->nlocal * sizeof(double), hipMemcpyDeviceToDevice,
                           ctx->stream));
@@ -147,7 +145,8 @@ static int cheb_bounds(pb_ksp* k) {
   if (given) {
     PB_TRY(check_cheb_pair(emin, emax, "chebyshev eigenvalues"));
     k->ch.state = 1;
-  } else if (k->ch.state != 2 || memcmp(dl, k->ch.deltas, sizeof(dl)) != 0) {
+  } else if (k->ch.state != 2 || memcmp(dl, k->ch.deltas, sizeof(dl)) != 0 ||
+             k->ch.change[0] != k->A->change || k->ch.change[1] != k->P->change) {
     if (k->begun) return set_error(PB_ERR_STATE, "Chebyshev eigenvalue estimate inside a solve");
     double lo = 0.0, hi = 0.0;
     int m = 0;
@@ -165,6 +164,8 @@ static int cheb_bounds(pb_ksp* k) {
                        "-ksp_chebyshev_esteig weights that keep emax > emin, or explicit "
                        "-ksp_chebyshev_eigenvalues)", lo, hi, emin, emax);
     memcpy(k->ch.deltas, dl, sizeof(dl));
+    k->ch.change[0] = k->A->change;
+    k->ch.change[1] = k->P->change;
     k->ch.state = 2;
   } else {
     emin = k->ch.emin;
@@ -296,8 +297,8 @@ int pb::solve_preonly(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res)
   if (k->fft) {
     PB_TRY(fftpc_apply(k->fft, b->d, x->d));
   } else {
-    if (k->mg) {
-      PB_TRY(mg_apply(k->mg, b->d, x->d));
+    if (k->stored_z()) {  // mg, sor or the Jacobi PC of a variable P
+      PB_TRY(pc_stored_apply(k, b->d, x->d));
       if (k->opts.nullspace) PB_TRY(launch_pre_scale_sum(g, x->d, nullptr, 1.0, &np));
     } else {
       const double dinv = k->opts.pc_type == PB_PC_JACOBI ? 1.0 / k->P->cc : 1.0;

@@ -19,8 +19,33 @@ static int star7_apply(pb_op* op, const double* x, double* y) {
                       });
 }
 
+// y = div(beta grad x) (pb_varcoef.hip). One rank: the wrap planes of x read in place; split
+// grids: x's boundary planes through halo_overlap (beta's ghost planes are the operator's own).
+// nparts != nullptr: the per-block partial sums of x . y ride along (*nparts blocks at block 0)
+static int varcoef_apply(pb_op* op, const double* x, double* y, int* nparts) {
+  pb_grid* g = op->grid;
+  const VarCoef c = varcoef_of(op);
+  int none = 0;
+  return halo_overlap(g, x, x + (g->nzl - 1) * g->plane, wrap_planes(), "varcoef", 0,
+                      nparts ? nparts : &none,
+                      [&](int mode, const StencilPlanes& gp, int part_off, int* nb) {
+                        return launch_varcoef_apply(g, c, x, y, gp, mode, nparts != nullptr,
+                                                    part_off, nb);
+                      });
+}
+
+int pb::op_apply_dot(pb_op* op, const double* p, double* w, int* nparts) {
+  *nparts = 0;
+  // (default 1: at 512^3 the fused form saves the dot kernel's 0.36 ms per iteration, six times the
+  // unfused launches' own spread, and costs the operator's pass nothing)
+  if (op->kind == PB_OP_VARCOEF && tune("varcoef_dot_fused", 1) != 0)
+    return varcoef_apply(op, p, w, nparts);
+  return op_apply_raw(op, p, w);
+}
+
 int pb::op_apply_raw(pb_op* op, const double* x, double* y) {
   pb_grid* g = op->grid;
+  if (op->kind == PB_OP_VARCOEF) return varcoef_apply(op, x, y, nullptr);
   if (op->kind == PB_OP_COMPACT) return compact_lapl_fast(g, op->deltas, x, y, op->work);
   PB_TRY(star7_apply(op, x, y));
   if (op->kind != PB_OP_ASSEMBLED27) return PB_OK;
@@ -38,7 +63,8 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 int pb_op_create(pb_grid* g, int kind, const double deltas[3], pb_op** out) {
   PB_CHECK_ARG(g && out, "bad op args");
-  PB_CHECK_ARG(kind == PB_OP_STAR7 || kind == PB_OP_COMPACT || kind == PB_OP_ASSEMBLED27,
+  PB_CHECK_ARG(kind == PB_OP_STAR7 || kind == PB_OP_COMPACT || kind == PB_OP_ASSEMBLED27 ||
+                   kind == PB_OP_VARCOEF,
                "unknown operator kind");
   pb_op* op = new pb_op();
   op->grid = g;
@@ -56,6 +82,20 @@ int pb_op_create(pb_grid* g, int kind, const double deltas[3], pb_op** out) {
       return set_error(PB_ERR_ALLOC, "compact operator workspace: out of device memory");
     }
   }
+  if (kind == PB_OP_VARCOEF) {
+    // one field and two ghost planes; beta = 1 everywhere, the ghosts included
+    const int64_t len = g->nlocal + 2 * g->plane;
+    if (field_alloc(&op->beta_store, (size_t)len * sizeof(double)) != hipSuccess) {
+      delete op;
+      return set_error(PB_ERR_ALLOC, "variable-coefficient operator: out of device memory");
+    }
+    op->beta = op->beta_store + g->plane;
+    if (const int rc = vec_fill(g->ctx, op->beta_store, len, 1.0)) {
+      field_free(op->beta_store);
+      delete op;
+      return rc;
+    }
+  }
   *out = op;
   return PB_OK;
 }
@@ -68,6 +108,64 @@ int pb_op_set_deltas(pb_op* op, const double deltas[3]) {
   op->cy = s.cy;
   op->cz = s.cz;
   op->cc = s.cc;
+  ++op->change;  // what a KSP derived from the old deltas is rebuilt
+  return PB_OK;
+}
+
+static int varcoef_only(const pb_op* op, const char* what) {
+  if (op->kind != PB_OP_VARCOEF)
+    return set_error(PB_ERR_STATE, "%s needs a PB_OP_VARCOEF operator", what);
+  return PB_OK;
+}
+
+int pb_op_set_coefficient(pb_op* op, const pb_vec* beta, int mean) {
+  PB_CHECK_ARG(op && beta, "bad args");
+  PB_TRY(varcoef_only(op, "pb_op_set_coefficient"));
+  if (op->in_solve > 0)
+    return set_error(PB_ERR_STATE, "pb_op_set_coefficient inside a solve that holds the operator");
+  PB_CHECK_ARG(mean == PB_COEF_ARITHMETIC || mean == PB_COEF_HARMONIC, "unknown coefficient mean");
+  pb_grid* g = op->grid;
+  PB_CHECK_ARG(beta->grid == g, "vector/operator grid mismatch");
+  // checked on the caller's vector, over all ranks, before anything of the operator changes
+  double bad = 0.0;
+  PB_TRY(varcoef_count_bad(g, beta->d, &bad));
+  if (bad != 0.0)
+    return set_error(PB_ERR_ARG, "coefficient field: %.0f values are not finite and > 0", bad);
+  pb_ctx* ctx = g->ctx;
+  PB_HIP(hipMemcpyAsync(op->beta, beta->d, (size_t)g->nlocal * sizeof(double),
+                        hipMemcpyDeviceToDevice, ctx->stream));
+  // the ghost planes: the neighbouring ranks' boundary planes (one rank: the periodic wrap)
+  PB_TRY(halo_exchange_n(g, op->beta, op->beta + (g->nzl - 1) * g->plane, 1, op->beta_store,
+                         op->beta + g->nlocal));
+  PB_SYNC(ctx, "pb_op_set_coefficient");
+  op->mean = mean;
+  ++op->change;
+  return PB_OK;
+}
+
+int pb_op_get_coefficient(const pb_op* op, pb_vec* beta, int* mean) {
+  PB_CHECK_ARG(op, "bad args");
+  PB_TRY(varcoef_only(op, "pb_op_get_coefficient"));
+  if (beta) {
+    pb_grid* g = op->grid;
+    PB_CHECK_ARG(beta->grid == g, "vector/operator grid mismatch");
+    PB_HIP(hipMemcpyAsync(beta->d, op->beta, (size_t)g->nlocal * sizeof(double),
+                          hipMemcpyDeviceToDevice, g->ctx->stream));
+    PB_SYNC(g->ctx, "pb_op_get_coefficient");
+  }
+  if (mean) *mean = op->mean;
+  return PB_OK;
+}
+
+int pb_op_get_diagonal_vec(const pb_op* op, pb_vec* diag) {
+  PB_CHECK_ARG(op && diag, "bad args");
+  pb_grid* g = op->grid;
+  PB_CHECK_ARG(diag->grid == g, "vector/operator grid mismatch");
+  if (op->kind == PB_OP_COMPACT)
+    return set_error(PB_ERR_UNSUPPORTED, "the compact operator has no stored diagonal");
+  if (op->kind == PB_OP_VARCOEF) PB_TRY(launch_varcoef_diag(g, varcoef_of(op), diag->d, false));
+  else PB_TRY(vec_fill(g->ctx, diag->d, g->nlocal, op->cc));
+  PB_SYNC(g->ctx, "pb_op_get_diagonal_vec");
   return PB_OK;
 }
 
@@ -96,16 +194,19 @@ int pb_vec_get_ownership_range(const pb_vec* v, int64_t* first, int64_t* next) {
 
 int pb_op_get_diagonal(const pb_op* op, double* diag) {
   PB_CHECK_ARG(op && diag, "bad args");
+  if (op->kind == PB_OP_VARCOEF)
+    return set_error(PB_ERR_UNSUPPORTED,
+                     "the diagonal of PB_OP_VARCOEF is a field: use pb_op_get_diagonal_vec");
   *diag = op->cc;
   return PB_OK;
 }
 
 int pb_op_destroy(pb_op* op) {
   if (!op) return PB_OK;
-  if (op->work) {
+  if (op->work || op->beta_store)
     (void)wait_stream(op->grid->ctx, op->grid->ctx->stream, "pb_op_destroy");
-    (void)hipFree(op->work);
-  }
+  if (op->work) (void)hipFree(op->work);
+  field_free(op->beta_store);
   delete op;
   return PB_OK;
 }

@@ -35,10 +35,26 @@ int pb::ensure_done_cap(pb_ksp* k, int64_t need) {
   return PB_OK;
 }
 
+// z = M^-1 r of a stored-z preconditioner, nothing else (no sums, no null-space shift)
+int pb::pc_stored_apply(pb_ksp* k, const double* r, double* z, const int* skip) {
+  if (k->fft) return fftpc_apply(k->fft, r, z, skip);
+  if (k->mg) return mg_apply(k->mg, r, z, skip);
+  // the Jacobi PC of a variable P: the reciprocal diagonal of P as it is now
+  pb_grid* g = k->P->grid;
+  if (!k->vj.dinv && field_alloc(&k->vj.dinv, (size_t)g->nlocal * sizeof(double)) != hipSuccess)
+    return set_error(PB_ERR_ALLOC, "Jacobi diagonal: out of device memory");
+  if (k->vj.seen != k->P->change) {
+    PB_TRY(launch_varcoef_diag(g, varcoef_of(k->P), k->vj.dinv, true));
+    k->vj.seen = k->P->change;
+  }
+  return launch_varcoef_jacobi(g, k->vj.dinv, r, z, skip);
+}
+
 // z = M^-1 r for the stored-z preconditioners; *np = residual-sum partial blocks written by the
 // PC itself (MG's last sweep), 0 if the caller must take the sums
 int pb::pc_apply_dev(pb_ksp* k, const double* r, double* z, const int* skip, int* np) {
   *np = 0;
+  if (k->vj.on) return pc_stored_apply(k, r, z, skip);
   if (k->fft) return fftpc_apply(k->fft, r, z, skip, k->d_st, np);
   return mg_apply(k->mg, r, z, skip, k->d_st, np);
 }
@@ -95,6 +111,12 @@ int pb_ksp_create(pb_op* A, pb_op* P, const pb_ksp_opts* opts, pb_ksp** out) {
     return fail(set_error(PB_ERR_UNSUPPORTED, "unknown pc_type %d", pc));
   pb_grid* g = A->grid;
   const size_t vb = (size_t)g->nlocal * sizeof(double);
+  if (P->kind == PB_OP_VARCOEF && (pc == PB_PC_SOR || pc == PB_PC_MG || pc == PB_PC_FFT))
+    return fail(set_error(PB_ERR_UNSUPPORTED,
+                          "-pc_type sor / mg / fft cannot be built from a PB_OP_VARCOEF P: pass a "
+                          "constant-coefficient P (PB_OP_STAR7 or PB_OP_ASSEMBLED27) for the "
+                          "preconditioner, or use -pc_type jacobi / none"));
+  k->vj.on = P->kind == PB_OP_VARCOEF && pc == PB_PC_JACOBI;
   if (pc == PB_PC_SOR || pc == PB_PC_MG) {
     // the smoother / coarse operators are the 7-point P (src/coefficients.f90 star)
     if (P->kind == PB_OP_COMPACT)
@@ -174,12 +196,12 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   st.dtol = k->opts.dtol;
   st.max_it = k->opts.max_it;
   st.nhist = k->nhist;
-  st.pc = k->opts.pc_type;
+  st.pc = k->vj.on ? (int)PC_JACOBI_FIELD : k->opts.pc_type;
   st.nullspace = k->opts.nullspace;
   st.norm = k->norm();
   // PCJacobi stores the reciprocal of diag(P) (src/coefficients.f90:44-46 centre coefficient);
   // with SOR / MG the sums are taken over z = M^-1 r itself (dinv = 1)
-  st.dinv = k->opts.pc_type == PB_PC_JACOBI ? 1.0 / k->P->cc : 1.0;
+  st.dinv = k->opts.pc_type == PB_PC_JACOBI && !k->vj.on ? 1.0 / k->P->cc : 1.0;
   st.ntot = (double)(g->n[0] * g->n[1] * g->n[2]);
   // (cg uploads the state itself, with the form of this solve's iteration in it)
   if (!k->cg())
@@ -193,6 +215,10 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   k->x = x;
   k->host_iter = 0;
   k->stopped = k->h_done[0] != 0;
+  if (!k->begun) {  // (pb_op_set_coefficient is PB_ERR_STATE until pb_ksp_end)
+    ++k->A->in_solve;
+    if (k->P != k->A) ++k->P->in_solve;
+  }
   k->begun = true;
   return PB_OK;
 }
@@ -299,6 +325,8 @@ int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
     }
     fflush(stdout);
   }
+  --k->A->in_solve;
+  if (k->P != k->A) --k->P->in_solve;
   k->begun = false;
   return PB_OK;
 }
@@ -317,6 +345,10 @@ int pb_ksp_solve(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, doub
 int pb_ksp_destroy(pb_ksp* k) {
   if (!k) return PB_OK;
   (void)wait_stream(k->A->grid->ctx, k->A->grid->ctx->stream, "pb_ksp_destroy");
+  if (k->begun) {  // destroyed inside a solve: the operators are free again
+    --k->A->in_solve;
+    if (k->P != k->A) --k->P->in_solve;
+  }
   field_free(k->r);
   field_free(k->r2);
   for (double* p : k->pb) field_free(p);
@@ -324,6 +356,7 @@ int pb_ksp_destroy(pb_ksp* k) {
   field_free(k->z);
   field_free(k->ri.x2);
   field_free(k->ri.x3);
+  field_free(k->vj.dinv);
   fgmres_destroy(k);
   pipecg_destroy(k);
   if (k->mg) mg_destroy(k->mg);
@@ -348,10 +381,8 @@ int pb_ksp_pc_apply(pb_ksp* k, const pb_vec* r, pb_vec* z) {
   pb_grid* g = k->A->grid;
   PB_CHECK_ARG(r->grid == g && z->grid == g, "vector/operator grid mismatch");
   pb_ctx* ctx = g->ctx;
-  if (k->mg) {
-    PB_TRY(mg_apply(k->mg, r->d, z->d));
-  } else if (k->fft) {
-    PB_TRY(fftpc_apply(k->fft, r->d, z->d));
+  if (k->stored_z()) {
+    PB_TRY(pc_stored_apply(k, r->d, z->d));
   } else {
     PB_HIP(hipMemcpyAsync(z->d, r->d, (size_t)g->nlocal * sizeof(double),
                           hipMemcpyDeviceToDevice, ctx->stream));

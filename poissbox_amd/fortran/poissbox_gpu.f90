@@ -96,6 +96,9 @@ module poissbox_gpu
   end type pb_ksp_result
 
   integer(c_int), parameter, public :: PB_OP_STAR7 = 0, PB_OP_COMPACT = 1, PB_OP_ASSEMBLED27 = 2
+  !! div(beta grad) with beta per cell (pb_op_set_coefficient) and the mean of its face values
+  integer(c_int), parameter, public :: PB_OP_VARCOEF = 3
+  integer(c_int), parameter, public :: PB_COEF_ARITHMETIC = 0, PB_COEF_HARMONIC = 1
   !! -ksp_norm_type (pb_ksp_norm_type: PETSc's KSPNormType values)
   integer(c_int), parameter, public :: PB_KSP_NORM_DEFAULT = -1, PB_KSP_NORM_NONE = 0
   integer(c_int), parameter, public :: PB_KSP_NORM_PRECONDITIONED = 1
@@ -133,6 +136,9 @@ module poissbox_gpu
   public :: c_pb_ksp_norm_type_parse, c_pb_ksp_set_norm_type, c_pb_ksp_get_norm_type
   public :: c_pb_ksp_opts_default, c_pb_ksp_opts_parse
   public :: c_pb_ksp_create, c_pb_ksp_solve, c_pb_ksp_destroy
+  ! PB_OP_VARCOEF: the coefficient field and the diagonal as a vector (op, beta, diag: the handles
+  ! of a Mat / Vec, their component h)
+  public :: c_pb_op_set_coefficient, c_pb_op_get_coefficient, c_pb_op_get_diagonal_vec
 
   interface PoissboxAllreduceSum  ! ≙ MPI_Allreduce(..., MPI_SUM, MPI_COMM_WORLD)
      module procedure allreduce_sum_int, allreduce_sum_real
@@ -181,6 +187,23 @@ module poissbox_gpu
        import :: c_int, c_ptr, c_double
        type(c_ptr), value :: op
        real(c_double), dimension(3) :: deltas
+     end function
+     integer(c_int) function c_pb_op_set_coefficient(op, beta, mean) &
+          bind(C, name="pb_op_set_coefficient")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: op, beta
+       integer(c_int), value :: mean
+     end function
+     integer(c_int) function c_pb_op_get_coefficient(op, beta, mean) &
+          bind(C, name="pb_op_get_coefficient")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: op, beta
+       integer(c_int) :: mean
+     end function
+     integer(c_int) function c_pb_op_get_diagonal_vec(op, diag) &
+          bind(C, name="pb_op_get_diagonal_vec")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: op, diag
      end function
      ! src/tridsol.f90 on device pointers (element e of line l at ptr[l*line_stride + e*elem_stride])
      integer(c_int) function c_pb_tdma_batched(ctx, n, nbatch, ls, es, a, b, c, d, periodic) &
