@@ -601,6 +601,20 @@ int pb_tridiag_extreme_eigenvalues(int n, const double* diag, const double* off,
 int pb_ksp_pc_apply(pb_ksp* ksp, const pb_vec* r, pb_vec* z);
 /* number of multigrid levels in use (1 for SOR, 0 for Jacobi / none) */
 int pb_ksp_pc_levels(const pb_ksp* ksp, int* levels);
+/* The variable-coefficient SOR / multigrid preconditioner. -pc_type sor | mg only (else
+ * PB_ERR_STATE), on a KSP created with a constant-coefficient 7-point P. C: a PB_OP_VARCOEF
+ * operator of the KSP's grid (usually A; another kind or grid: PB_ERR_ARG); NULL returns to the
+ * constant-coefficient PC. From the next solve / pb_ksp_pc_apply on, the smoother, the residual and
+ * every coarse operator are div(beta_l grad) with C's mean and C's deltas (h_l = 2^l h), beta_0 =
+ * C's coefficient and beta_(l+1) the arithmetic mean of a cell's 8 children; P's deltas are no
+ * longer read by the PC. The KSP holds C as it holds A and P (pb_op_set_coefficient(C) inside a
+ * solve is PB_ERR_STATE; C must outlive the KSP or be unset first); the levels are rebuilt by the
+ * first apply after pb_op_set_coefficient(C) / pb_op_set_deltas(C). Level smoothers: richardson +
+ * sor with 1..8 sweeps; a Jacobi-type level smoother together with a coefficient is
+ * PB_ERR_UNSUPPORTED, from whichever of the two calls comes second. PB_ERR_STATE inside a solve.
+ * Every error leaves the KSP as it was. */
+int pb_ksp_pc_set_coefficient_from(pb_ksp* ksp, const pb_op* C);
+int pb_ksp_pc_get_coefficient_from(const pb_ksp* ksp, const pb_op** C);
 /* Projected initial guess (guess_type = PB_GUESS_FISCHER; every call returns PB_ERR_STATE on a
  * KSP created without it). pb_ksp_solve calls form before and update after the solve by itself;
  * callers of the split form (pb_ksp_begin with initial_guess_nonzero = 1) call them around it.

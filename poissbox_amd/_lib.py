@@ -156,6 +156,8 @@ _SIGS = {
     "pb_tridiag_extreme_eigenvalues": [C.c_int, P_d, P_d, P_d, P_d],
     "pb_ksp_pc_apply": [c_p, c_p, c_p],
     "pb_ksp_pc_levels": [c_p, C.POINTER(C.c_int)],
+    "pb_ksp_pc_set_coefficient_from": [c_p, c_p],
+    "pb_ksp_pc_get_coefficient_from": [c_p, C.POINTER(c_p)],
     "pb_solve": [c_p, c_p, C.POINTER(KspOpts), c_p, c_p, C.POINTER(KspResult), P_d, c_i64],
     "pb_tdma_batched": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, C.c_int],
     "pb_pcr_alpha_batched": [c_p, c_i64, c_i64, c_i64, c_i64, c_d, c_p],

@@ -664,6 +664,23 @@ class KSP:
         L.call("pb_ksp_pc_levels", self.h, C.byref(v))
         return v.value
 
+    def pc_set_coefficient_from(self, op):
+        """pb_ksp_pc_set_coefficient_from: the -pc_type sor | mg levels become div(beta_l grad) of
+        the VARCOEF Mat `op` (usually A); None returns to the constant-coefficient PC. The KSP
+        holds op: keep it alive until the KSP is destroyed or the coefficient is unset."""
+        L.call("pb_ksp_pc_set_coefficient_from", self.h, op.h if op is not None else None)
+        self._pc_coef = op
+
+    def pc_coefficient_from(self):
+        """The Mat given to pc_set_coefficient_from, or None."""
+        h = C.c_void_p()
+        L.call("pb_ksp_pc_get_coefficient_from", self.h, C.byref(h))
+        if not h.value:
+            return None
+        op = getattr(self, "_pc_coef", None)
+        assert op is not None and op.h.value == h.value
+        return op
+
     def destroy(self):
         if self.h:
             L.call("pb_ksp_destroy", self.h)

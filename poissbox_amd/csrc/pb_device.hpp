@@ -8,6 +8,19 @@ namespace pb {
 
 typedef double dv2 __attribute__((ext_vector_type(2)));
 
+// the face mean of PB_OP_VARCOEF (pb_varcoef.hip) and of its multigrid levels (pb_mg_varcoef.hip):
+// arithmetic 0.5 (a + b) | harmonic (2 (a b)) / (a + b), every operation rounded
+template <int HARM>
+__device__ __forceinline__ double vc_face(double a, double b) {
+  const double s = a + b;
+  if constexpr (HARM) {
+    const double pr = a * b;
+    return (2.0 * pr) / s;
+  } else {
+    return 0.5 * s;
+  }
+}
+
 #ifndef PB_KWAVES
 #define PB_KWAVES 4  // waves per workgroup (stacked in y)
 #endif

@@ -339,6 +339,10 @@ inline VarCoef varcoef_of(const pb_op* op) {
 // ctx->op_skip as launch_star7_apply does
 int launch_varcoef_apply(pb_grid* g, const VarCoef& c, const double* x, double* y,
                          const StencilPlanes& gp, int mode, bool dot, int part_off, int* nblocks);
+// res = b - A x over all planes by the same kernel (the variable multigrid's residual pass); exits
+// at entry when *skip is set
+int launch_varcoef_residual(pb_grid* g, const VarCoef& c, const double* x, const double* b,
+                            double* res, const StencilPlanes& gp, const int* skip);
 // out = diag(A), or its reciprocal (what PCJacobi stores)
 int launch_varcoef_diag(pb_grid* g, const VarCoef& c, double* out, bool recip);
 // *count = the values of v, over all ranks, that are not finite and > 0 (collective, synchronous)
@@ -802,6 +806,10 @@ struct MgSmoother {
   double rich_scale = 1.0, emin = 0.0, emax = 0.0;
 };
 int mg_set_smoother(Mg* mg, const MgSmoother& sm);
+// the variable-coefficient PC: C = a PB_OP_VARCOEF operator on the hierarchy's grid whose beta,
+// mean and deltas define every level's operator (held, not owned; rebuilt by the first apply after
+// C->change moved), nullptr = the constant-coefficient levels again
+int mg_set_coefficient(Mg* mg, const pb_op* C);
 void mg_destroy(Mg* mg);
 // deterministic level count for a global grid split over nranks z-slabs (every rank agrees)
 int mg_plan_levels(const int64_t n[3], int nranks, int levels_req);

@@ -116,6 +116,13 @@ struct pb_ksp {
   bool cg() const { return !rich() && !fgmres() && !pipecg(); }
   pb::Mg* mg = nullptr;  // SOR / multigrid preconditioner (PB_PC_SOR, PB_PC_MG)
   pb_pc_mg_opts mgopts;  // pb_ksp_pc_mg_set_opts; the defaults from pb_ksp_create
+  // pb_ksp_pc_set_coefficient_from: the PB_OP_VARCOEF operator the SOR / MG levels take their
+  // coefficient from (held like A and P, not owned). pc_coef(): it, where a solve must hold it
+  // beside A and P
+  const pb_op* coef = nullptr;
+  pb_op* pc_coef() const {
+    return coef && coef != A && coef != P ? const_cast<pb_op*>(coef) : nullptr;
+  }
   pb::FftPc* fft = nullptr;  // spectral preconditioner (PB_PC_FFT)
   int fold_nparts_b = 0;     // partial-sum blocks of the last folded pass B
   // -pc_type jacobi from a PB_OP_VARCOEF P: the diagonal is a field, so z = dinv o r is stored like

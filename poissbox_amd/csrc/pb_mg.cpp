@@ -3,7 +3,9 @@
 // (level_plan) and runs down legs, the coarse solve or the one-launch tail, and up legs; a leg
 // switches on its level's plan and calls launchers (pb_mg.hpp, pb_internal.hpp). No kernel is named
 // here. The level smoothers (-mg_levels_*, Mg::custom()) run the same driver under a plan with
-// every fusion, the tail and the agglomeration off (restated in tests/mg_smoothers_restatement.py).
+// every fusion, the tail and the agglomeration off (restated in tests/mg_smoothers_restatement.py);
+// so do the variable-coefficient levels (mg_set_coefficient; their kernels: pb_mg_varcoef.hip,
+// restated in tests/varcoef_mg_restatement.py).
 #include <algorithm>
 #include <cmath>
 
@@ -43,6 +45,7 @@ void mg_destroy(Mg* mg) {
   if (mg->mem) (void)hipFree(mg->mem);
   if (mg->agg) (void)hipFree(mg->agg);
   if (mg->pmem) (void)hipFree(mg->pmem);
+  if (mg->vmem) (void)hipFree(mg->vmem);
   delete mg;
 }
 
@@ -59,6 +62,12 @@ static MgTune mg_tunings(const pb_ctx* ctx) {
   t.tail_max = tune("mg_tail_max", 8192);
   t.split_fused = tune("mg_split_fused", 1) != 0;
   t.poly_fused = tune("mg_poly_fused", 1) != 0;
+  // the variable-coefficient levels (measured at 512^3): the one-pass zero-start
+  // pre-smoothing 1.94 ms against 2.30 ms for its two launches (their spread 0.03); the in-place
+  // half-sweep 1.51 ms forming dinv from its faces against 1.66 ms reading the stored field
+  t.vc_pre_fused = tune("mg_varcoef_pre_fused", 1) != 0;
+  t.vc_dinv_stored = tune("mg_varcoef_dinv_stored", 0) != 0;
+  t.vc_kc = tune("mg_varcoef_kc", 0);
   return t;
 }
 
@@ -232,6 +241,33 @@ int mg_set_smoother(Mg* mg, const MgSmoother& sm) {
   return PB_OK;
 }
 
+// C: a PB_OP_VARCOEF operator on the hierarchy's grid (checked by the caller), nullptr: back to the
+// constant-coefficient levels. The levels' beta (below level 0) and dinv are allocated on the
+// first call, each with two ghost planes, and filled by the next apply (vmg_build)
+int mg_set_coefficient(Mg* mg, const pb_op* C) {
+  if (C && !mg->vmem) {
+    const int L = (int)mg->lv.size();
+    int64_t total = 0;
+    for (int l = 0; l < L; ++l)
+      total += (l > 0 ? 2 : 1) * (mg->lv[l].g->nlocal + 2 * mg->lv[l].g->plane);
+    if (hipMalloc(&mg->vmem, (size_t)total * sizeof(double)) != hipSuccess)
+      return set_error(PB_ERR_ALLOC, "multigrid level coefficients: out of device memory");
+    double* p = mg->vmem;
+    for (int l = 0; l < L; ++l) {
+      MgLevel& lv = mg->lv[l];
+      const int64_t len = lv.g->nlocal + 2 * lv.g->plane;
+      lv.dinv = p + lv.g->plane;
+      p += len;
+      if (l == 0) continue;
+      lv.beta_own = p + lv.g->plane;
+      p += len;
+    }
+  }
+  mg->coef = C;
+  mg->coef_seen = -1;
+  return PB_OK;
+}
+
 // coarsest level: `coarse_its` symmetric red-black sweeps from zero (red, black, red, black, ...)
 static int coarse_solve(Mg* mg, MgLevel& L, MgSums sums) {
   PB_TRY(level_smooth(mg, L, 0, 1));  // red from zero + black
@@ -382,6 +418,7 @@ int mg_apply(Mg* mg, const double* r, double* z, const int* skip, const CgState*
   mg->lv[0].b = const_cast<double*>(r);
   mg->lv[0].x = z;
   mg->tn = mg_tunings(ctx);
+  if (mg->coef && mg->coef_seen != mg->coef->change) PB_TRY(vmg_build(mg));
   for (int l = 0; l < L; ++l) mg->lv[l].plan = level_plan(mg, l, mg->lv[l].xs != nullptr);
   // the level smoothers: no sums (the caller takes CG's), no tail, no agglomeration
   const bool custom = mg->custom();

@@ -27,7 +27,9 @@
 //
 // This file: the per-pair, per-cell, polynomial and tail kernels and, at its end, the launchers
 // that name them, one per pass (pb_mg.hpp). The host path -- hierarchy, level plan, driver and
-// legs -- is pb_mg.cpp; the fused sweeps are pb_mg_sweep.hip, the engine passes pb_mg_engine.hip.
+// legs -- is pb_mg.cpp; the fused sweeps are pb_mg_sweep.hip, the engine passes pb_mg_engine.hip,
+// the variable-coefficient levels' half-sweeps and residual (level_smooth's and level_residual's
+// branch under Mg::coef) pb_mg_varcoef.hip.
 #include <algorithm>
 #include <type_traits>
 
@@ -631,8 +633,7 @@ static int mg_blocks(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)1 << 30));
 }
 
-// ghost planes of v on level L: in place (1 rank) or exchanged (N ranks)
-static int ghosts(MgLevel& L, const double* v, const double** lo, const double** hi) {
+int level_ghosts(MgLevel& L, const double* v, const double** lo, const double** hi) {
   pb_grid* g = L.g;
   if (!g->ctx->split) {
     *lo = v + (g->nzl - 1) * g->plane;
@@ -646,8 +647,9 @@ static int ghosts(MgLevel& L, const double* v, const double** lo, const double**
 }
 
 int level_smooth(Mg* mg, MgLevel& L, int color, int mode, MgSums sums) {
+  if (mg->coef) return vmg_smooth(mg, L, color, mode);
   const double *lo = nullptr, *hi = nullptr;
-  PB_TRY(ghosts(L, mode == 1 ? L.b : L.x, &lo, &hi));
+  PB_TRY(level_ghosts(L, mode == 1 ? L.b : L.x, &lo, &hi));
   if (L.plan.engine) {
     const StencilPlanes gp{lo, hi};
     return launch_mg_sor(L.g, L.s, L.x, L.b, gp, mg->omega, color, mode == 1, mg->skip,
@@ -662,8 +664,9 @@ int level_smooth(Mg* mg, MgLevel& L, int color, int mode, MgSums sums) {
 }
 
 int level_residual(Mg* mg, MgLevel& F, const double* x, double* res) {
+  if (mg->coef) return vmg_residual(mg, F, x, res);
   const double *lo, *hi;
-  PB_TRY(ghosts(F, x, &lo, &hi));
+  PB_TRY(level_ghosts(F, x, &lo, &hi));
   if (F.plan.engine)
     return launch_mg_residual(F.g, F.s, x, F.b, StencilPlanes{lo, hi}, res, mg->skip);
   const MgGeo G = F.geo();
@@ -675,7 +678,7 @@ int level_residual(Mg* mg, MgLevel& F, const double* x, double* res) {
 
 int level_restrict(Mg* mg, MgLevel& F, const double* res, MgLevel& C) {
   const double *lo, *hi;
-  PB_TRY(ghosts(F, res, &lo, &hi));
+  PB_TRY(level_ghosts(F, res, &lo, &hi));
   const MgGeo G = F.geo(), CG = C.geo();
   if (F.plan.march) {
     const int64_t cols = (int64_t)CG.nx * CG.ny;
@@ -695,7 +698,7 @@ int level_prolong(Mg* mg, MgLevel& F, const double* xf, double* xout, MgLevel& C
                   const CoarsePlanes* cp) {
   CoarsePlanes p{C.x, nullptr, nullptr};
   if (cp) p = *cp;
-  else PB_TRY(ghosts(C, C.x, &p.lo, &p.hi));
+  else PB_TRY(level_ghosts(C, C.x, &p.lo, &p.hi));
   const MgGeo G = F.geo(), CG = C.geo();
   if (F.plan.march) {
     const int64_t cols = (int64_t)CG.nx * CG.ny;

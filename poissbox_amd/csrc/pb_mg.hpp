@@ -1,7 +1,8 @@
 // pb_mg.hpp -- what the multigrid preconditioner's files share: pb_mg.cpp (the host path: the
 // hierarchy, the level plan, the V-cycle driver and its legs) and pb_mg.hip (the per-pair,
-// per-cell, polynomial and tail kernels, each behind the one launcher that names it). The fused
-// sweeps (pb_mg_sweep.hip) and the engine passes (pb_mg_engine.hip): pb_internal.hpp.
+// per-cell, polynomial and tail kernels, each behind the one launcher that names it) and
+// pb_mg_varcoef.hip (the variable-coefficient levels). The fused sweeps (pb_mg_sweep.hip) and the
+// engine passes (pb_mg_engine.hip): pb_internal.hpp.
 #pragma once
 #include <vector>
 
@@ -47,6 +48,14 @@ struct MgLevel {
   double* t1 = nullptr;
   double* t2 = nullptr;
   double* r2 = nullptr;
+  // the variable-coefficient PC (mg_set_coefficient; pb_mg_varcoef.hip): the level's beta and the
+  // reciprocal diagonal of div(beta_l grad), each nzl + 2 planes with local plane 0 at the pointer
+  // (planes -1 and nzl: the neighbouring ranks', one rank: the periodic wrap). Level 0's beta is
+  // the operator's own storage; vs = the axis coefficients 1 / (2^l h_d)^2 of the operator's deltas
+  const double* beta = nullptr;
+  double* beta_own = nullptr;  // (below level 0: beta, writable)
+  double* dinv = nullptr;
+  Star vs;
   LevelPlan plan;         // this apply's
   double* cur = nullptr;  // this apply's pre-smoothed iterate, from the down leg to the up leg
   int64_t size() const { return n[0] * n[1] * n[2]; }  // of the whole grid
@@ -67,6 +76,10 @@ struct MgTune {
   int64_t tail_max;  // the one-launch tail: levels of at most this many points
   bool split_fused;  // decomposed grids: the unrolled fused passes with deep ghost planes
   bool poly_fused;   // Jacobi-type smoothers, one rank: a step and its residual in one pass
+  // variable-coefficient levels: the zero-start red + black half-sweeps in one pass | the
+  // half-sweep reads the stored dinv (else it forms it from its six faces)
+  bool vc_pre_fused, vc_dinv_stored;
+  int vc_kc;  // planes per chunk of the marching half-sweeps (0: by the level's size)
 };
 
 // CG's residual sums of the V-cycle's output, taken by its last pass where that pass can
@@ -107,8 +120,15 @@ struct Mg {
   // one sweep per leg -- a plan with every fusion, the tail and the agglomeration off
   MgSmoother sm;
   bool poly() const { return sm.pc == PB_MG_LEVELS_JACOBI; }
-  bool custom() const { return poly() || sm.nu > 1; }
+  bool custom() const { return poly() || sm.nu > 1 || coef; }
   double* pmem = nullptr;  // the levels' t1, t2, r2
+  // pb_ksp_pc_set_coefficient_from: smoother, residual and coarse operators are div(beta_l grad)
+  // of this PB_OP_VARCOEF operator (held, not owned). The levels' coefficients are rebuilt by the
+  // first apply after coef->change moved on from coef_seen
+  const pb_op* coef = nullptr;
+  int64_t coef_seen = -1;
+  int mean = PB_COEF_ARITHMETIC;  // coef's at the last build
+  double* vmem = nullptr;         // the levels' beta (below level 0) and dinv
 };
 
 // ---- the launchers (pb_mg.hip): one per pass, used by every path of the driver ----
@@ -127,6 +147,15 @@ int level_prolong(Mg* mg, MgLevel& F, const double* xf, double* xout, MgLevel& C
 int poly_step(Mg* mg, MgLevel& F, const double* y, const double* yp, const double* r, double scale,
               double omega, double* y_out, double* r_out);
 int launch_tail(Mg* mg, int Lt, bool agg);  // levels Lt .. L-1 in one launch (agg: gathered)
+// ghost planes of v on level L: in place (1 rank) or exchanged (N ranks)
+int level_ghosts(MgLevel& L, const double* v, const double** lo, const double** hi);
+// ---- the variable-coefficient levels (pb_mg_varcoef.hip) ----
+// the levels' beta (8-child arithmetic mean of the finer level's, then the ghost planes) and dinv
+// from mg->coef as it is now
+int vmg_build(Mg* mg);
+// level_smooth's and level_residual's variable branches
+int vmg_smooth(Mg* mg, MgLevel& L, int color, int mode);
+int vmg_residual(Mg* mg, MgLevel& F, const double* x, double* res);
 #pragma GCC visibility pop
 
 }  // namespace pb

@@ -218,6 +218,7 @@ int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   if (!k->begun) {  // (pb_op_set_coefficient is PB_ERR_STATE until pb_ksp_end)
     ++k->A->in_solve;
     if (k->P != k->A) ++k->P->in_solve;
+    if (pb_op* c = k->pc_coef()) ++c->in_solve;
   }
   k->begun = true;
   return PB_OK;
@@ -327,6 +328,7 @@ int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
   }
   --k->A->in_solve;
   if (k->P != k->A) --k->P->in_solve;
+  if (pb_op* c = k->pc_coef()) --c->in_solve;
   k->begun = false;
   return PB_OK;
 }
@@ -348,6 +350,7 @@ int pb_ksp_destroy(pb_ksp* k) {
   if (k->begun) {  // destroyed inside a solve: the operators are free again
     --k->A->in_solve;
     if (k->P != k->A) --k->P->in_solve;
+    if (pb_op* c = k->pc_coef()) --c->in_solve;
   }
   field_free(k->r);
   field_free(k->r2);
@@ -405,6 +408,10 @@ int pb_ksp_pc_mg_set_opts(pb_ksp* k, const pb_pc_mg_opts* o) {
     return set_error(PB_ERR_STATE, "KSP created without -pc_type mg");
   if (k->begun) return set_error(PB_ERR_STATE, "pb_ksp_pc_mg_set_opts inside a solve");
   PB_TRY(check_mg_opts(o));
+  if (k->coef && o->levels_pc_type == PB_MG_LEVELS_JACOBI)
+    return set_error(PB_ERR_UNSUPPORTED,
+                     "a Jacobi-type level smoother with pb_ksp_pc_set_coefficient_from: the "
+                     "variable-coefficient levels smooth with -mg_levels_pc_type sor");
   MgSmoother sm;
   sm.ksp = o->levels_ksp_type;
   sm.pc = o->levels_pc_type;
@@ -414,6 +421,33 @@ int pb_ksp_pc_mg_set_opts(pb_ksp* k, const pb_pc_mg_opts* o) {
   PB_TRY(mg_set_smoother(k->mg, sm));
   k->mgopts = *o;
   k->ch.state = 0;  // an outer Chebyshev's estimate belongs to the old preconditioner
+  return PB_OK;
+}
+
+int pb_ksp_pc_set_coefficient_from(pb_ksp* k, const pb_op* C) {
+  PB_CHECK_ARG(k, "ksp is NULL");
+  if (!k->mg)
+    return set_error(PB_ERR_STATE,
+                     "pb_ksp_pc_set_coefficient_from needs -pc_type sor or mg (the spectral PC "
+                     "cannot diagonalise a variable operator; Jacobi takes a PB_OP_VARCOEF P)");
+  if (k->begun) return set_error(PB_ERR_STATE, "pb_ksp_pc_set_coefficient_from inside a solve");
+  if (C) {
+    PB_CHECK_ARG(C->kind == PB_OP_VARCOEF, "the coefficient comes from a PB_OP_VARCOEF operator");
+    PB_CHECK_ARG(C->grid == k->A->grid, "coefficient operator and KSP on different grids");
+    if (k->mgopts.levels_pc_type == PB_MG_LEVELS_JACOBI)
+      return set_error(PB_ERR_UNSUPPORTED,
+                       "pb_ksp_pc_set_coefficient_from with a Jacobi-type level smoother: the "
+                       "variable-coefficient levels smooth with -mg_levels_pc_type sor");
+  }
+  PB_TRY(mg_set_coefficient(k->mg, C));
+  k->coef = C;
+  k->ch.state = 0;  // an outer Chebyshev's estimate belongs to the old preconditioner
+  return PB_OK;
+}
+
+int pb_ksp_pc_get_coefficient_from(const pb_ksp* k, const pb_op** C) {
+  PB_CHECK_ARG(k && C, "bad args");
+  *C = k->coef;
   return PB_OK;
 }
 

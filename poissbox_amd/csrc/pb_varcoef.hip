@@ -22,17 +22,6 @@
 
 namespace pb {
 
-template <int HARM>
-__device__ __forceinline__ double vc_face(double a, double b) {
-  const double s = a + b;
-  if constexpr (HARM) {
-    const double pr = a * b;
-    return (2.0 * pr) / s;
-  } else {
-    return 0.5 * s;
-  }
-}
-
 // The rows j0 .. j0 + TY - 1 of plane kk in [-1, nzl] of x and beta. The pointers come by value: a
 // select between references to the kernel's arguments would keep the arguments in scratch
 template <int V, int TY>
@@ -59,12 +48,14 @@ __device__ __forceinline__ void vc_issue_rows(int kk, int nzl, int wrap, int64_t
 // pb_op_set_coefficient: the neighbouring ranks' planes, on one rank the periodic wrap), so beta
 // needs no plane select. x's planes -1 / nzl: the wrap planes of x in place (g.wrap, one rank) or
 // the grid's ghost planes. parts != nullptr: the per-block partial sum of x . y (CG's p . Ap).
-template <int V, int TY, int HARM>
+// RES (the variable multigrid's residual pass, pb_mg_varcoef.hip): y = rb - A x instead of A x.
+template <int V, int TY, int HARM, int RES>
 __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, double cy, double cz,
                                                            const double* __restrict__ x,
                                                            const double* __restrict__ bt,
                                                            const double* __restrict__ ghost_lo,
                                                            const double* __restrict__ ghost_hi,
+                                                           const double* __restrict__ rb,
                                                            double* __restrict__ y, double* parts,
                                                            const int* __restrict__ skip) {
   if (skip && *skip) return;  // device-side convergence flag (uniform)
@@ -177,7 +168,8 @@ __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, dou
 #pragma unroll
         for (int e = 1; e < V; ++e) fx[e] = cx * vc_face<HARM>(b1[t][e - 1], b1[t][e]);
         fx[V] = cx * vc_face<HARM>(br, b1[t][V - 1]);
-        double w[V];
+        double w[V], rbv[V];
+        if constexpr (RES) load_row_nt<V>(rb, rix(base + (int64_t)(j0 + t) * nx), rbv);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           const double xc = x1[t][e];
@@ -192,7 +184,8 @@ __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, dou
           s = s + fx[e + 1] * (xp - xc);
           s = s + fy[t + 1][e] * (yp - xc);
           s = s + fzp * (x2[t][e] - xc);
-          w[e] = s;
+          if constexpr (RES) w[e] = rbv[e] - s;
+          else w[e] = s;
           fzm[t][e] = fzp;  // the face above plane k is the face below plane k + 1
           if (active) acc[0] += s * xc;
         }
@@ -206,10 +199,11 @@ __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, dou
   if (parts) block_partials<1>(acc, parts);
 }
 
+// rb != nullptr: y = rb - A x (no sums), exiting at entry on `skip` instead of ctx->op_skip
 template <int V, int TY, int HARM>
 static int launch_varcoef_t(pb_grid* g, const VarCoef& c, const double* x, double* y,
                             const StencilPlanes& gp, int mode, bool dot, int part_off,
-                            int* nblocks) {
+                            int* nblocks, const double* rb, const int* skip) {
   // workgroups per CU the z-chunks are sized for (two are resident at most: the registers).
   // Measured at 512^3 over 1, 2, 3, 4, 6: the arithmetic mean is fastest with 1 (four 128-plane
   // chunks), the harmonic mean, with its divisions to hide, with 3; 256^3 does not tell them apart
@@ -222,9 +216,14 @@ static int launch_varcoef_t(pb_grid* g, const VarCoef& c, const double* x, doubl
   if (dot && part_off + nb > g->ctx->partials_cap)
     return set_error(PB_ERR_UNSUPPORTED, "varcoef grid of %lld blocks exceeds partials capacity",
                      (long long)nb);
-  hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM>), dim3((unsigned)nb), dim3(kThreads), 0,
-                     g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo, gp.ghost_hi, y,
-                     dot ? g->ctx->d_partials + part_off : nullptr, g->ctx->op_skip);
+  if (rb)
+    hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM, 1>), dim3((unsigned)nb), dim3(kThreads), 0,
+                       g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo, gp.ghost_hi,
+                       rb, y, nullptr, skip);
+  else
+    hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM, 0>), dim3((unsigned)nb), dim3(kThreads), 0,
+                       g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo, gp.ghost_hi,
+                       rb, y, dot ? g->ctx->d_partials + part_off : nullptr, g->ctx->op_skip);
   PB_HIP(hipGetLastError());
   if (nblocks) *nblocks = dot ? (int)nb : 0;
   return PB_OK;
@@ -233,10 +232,10 @@ static int launch_varcoef_t(pb_grid* g, const VarCoef& c, const double* x, doubl
 template <int HARM>
 static int launch_varcoef_m(pb_grid* g, const VarCoef& c, const double* x, double* y,
                             const StencilPlanes& gp, int mode, bool dot, int part_off,
-                            int* nblocks) {
+                            int* nblocks, const double* rb = nullptr, const int* skip = nullptr) {
   const int ty = pick_ty((int)g->n[1]);
 #define PB_VC(V_, TY_) \
-  return launch_varcoef_t<V_, TY_, HARM>(g, c, x, y, gp, mode, dot, part_off, nblocks)
+  return launch_varcoef_t<V_, TY_, HARM>(g, c, x, y, gp, mode, dot, part_off, nblocks, rb, skip)
   if (g->n[0] % 2 == 0) {
     if (ty == 4) PB_VC(2, 4);
     if (ty == 2) PB_VC(2, 2);
@@ -254,6 +253,13 @@ int launch_varcoef_apply(pb_grid* g, const VarCoef& c, const double* x, double* 
   if (c.mean == PB_COEF_HARMONIC)
     return launch_varcoef_m<1>(g, c, x, y, gp, mode, dot, part_off, nblocks);
   return launch_varcoef_m<0>(g, c, x, y, gp, mode, dot, part_off, nblocks);
+}
+
+int launch_varcoef_residual(pb_grid* g, const VarCoef& c, const double* x, const double* b,
+                            double* res, const StencilPlanes& gp, const int* skip) {
+  if (c.mean == PB_COEF_HARMONIC)
+    return launch_varcoef_m<1>(g, c, x, res, gp, PLANES_ALL, false, 0, nullptr, b, skip);
+  return launch_varcoef_m<0>(g, c, x, res, gp, PLANES_ALL, false, 0, nullptr, b, skip);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -132,6 +132,7 @@ module poissbox_gpu
   ! -pc_type mg: the level smoother (-mg_levels_ksp_type, -mg_levels_pc_type, ...)
   public :: c_pb_pc_mg_opts_default, c_pb_pc_mg_opts_parse, c_pb_ksp_pc_mg_set_opts
   public :: c_pb_ksp_pc_mg_get_opts, c_pb_solve_mg
+  public :: c_pb_ksp_pc_set_coefficient_from, c_pb_ksp_pc_get_coefficient_from
   ! -ksp_norm_type (≙ KSPSetNormType / KSPGetNormType) and the KSP object it is set on
   public :: c_pb_ksp_norm_type_parse, c_pb_ksp_set_norm_type, c_pb_ksp_get_norm_type
   public :: c_pb_ksp_opts_default, c_pb_ksp_opts_parse
@@ -584,6 +585,19 @@ module poissbox_gpu
        import :: c_int, c_ptr, pb_pc_mg_opts
        type(c_ptr), value :: ksp
        type(pb_pc_mg_opts) :: o
+     end function
+     !! the variable-coefficient sor / mg levels from the PB_OP_VARCOEF operator coef (c_null_ptr:
+     !! the constant-coefficient PC again)
+     integer(c_int) function c_pb_ksp_pc_set_coefficient_from(ksp, coef) &
+          bind(C, name="pb_ksp_pc_set_coefficient_from")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp, coef
+     end function
+     integer(c_int) function c_pb_ksp_pc_get_coefficient_from(ksp, coef) &
+          bind(C, name="pb_ksp_pc_get_coefficient_from")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ksp
+       type(c_ptr) :: coef
      end function
      integer(c_int) function c_pb_solve_mg(A, P, o, mo, b, x, res, hist, cap) &
           bind(C, name="pb_solve_mg")
