@@ -244,7 +244,31 @@ int pb_op_set_coefficient(pb_op* op, const pb_vec* beta, int mean);
 /* The coefficient (copied into beta, a vector of the operator's grid) and the mean in force;
  * either may be NULL. PB_ERR_STATE on another kind. */
 int pb_op_get_coefficient(const pb_op* op, pb_vec* beta, int* mean);
-/* ≙ MatGetDiagonal: diag_c above for PB_OP_VARCOEF, the constant diagonal broadcast for
+/* The mass term of a PB_OP_VARCOEF operator: A = div(beta grad) - q with q_c = s * m_c (m NULL:
+ * q_c = s), the operator of an implicit diffusion / viscous / heat step (rho/dt) u - div(mu grad u)
+ * up to the sign. Every operation rounded:
+ *   y_c    = S6_c - q_c * x_c        S6_c: the six-term flux sum above
+ *   diag_c = (-G6_c) - q_c           G6_c: the six-term sum of the g_n above
+ * A stays symmetric to the bit, A 1 = -q to the bit, and A is negative definite as soon as q > 0
+ * somewhere. The term is on iff s != 0; with it off every launch is the one without the term. A
+ * scalar mass moves the 24 B/DoF of the plain apply, a field 32 B/DoF.
+ * Collective. PB_ERR_STATE on another kind, or between pb_ksp_begin and pb_ksp_end of a KSP that
+ * holds the operator. m is copied into storage the operator owns (one field, no ghost planes: q is
+ * point-local; freed when a later call passes NULL). Every value of m must be finite and >= 0 (zero:
+ * a region without mass; a device reduction over all ranks checks it), s finite and >= 0;
+ * PB_ERR_ARG otherwise or for a vector of another grid. An error leaves the operator as it was. A
+ * fresh operator has m absent and s = 0. A KSP holding the operator may be reused: the variable
+ * Jacobi's diagonal, the variable sor / mg levels (pb_ksp_pc_set_coefficient_from: q_0 = s * m,
+ * q_(l+1) the mean of a cell's 8 children) and Chebyshev's estimated bounds are rebuilt by its next
+ * solve -- a time loop with a changing dt calls pb_op_set_mass(op, rho, 1 / dt) per step.
+ * A KSP whose A has the term on solves a nonsingular system: with the option nullspace = 1
+ * pb_ksp_solve / pb_ksp_begin return PB_ERR_STATE before anything is enqueued; create it with
+ * nullspace = 0. The rule reads A only (a mass in P or in the PC's coefficient operator alone is a
+ * nonsingular preconditioner of a singular A). */
+int pb_op_set_mass(pb_op* op, const pb_vec* m, double s);
+/* The mass field (copied into m; ones where the operator's is absent) and s; either may be NULL. */
+int pb_op_get_mass(const pb_op* op, pb_vec* m, double* s);
+/* ≙ MatGetDiagonal: diag_c above (with the mass term) for PB_OP_VARCOEF, the constant diagonal broadcast for
  * PB_OP_STAR7 / PB_OP_ASSEMBLED27 (PB_ERR_UNSUPPORTED for PB_OP_COMPACT). */
 int pb_op_get_diagonal_vec(const pb_op* op, pb_vec* diag);
 int pb_op_destroy(pb_op* op);

@@ -115,6 +115,8 @@ _SIGS = {
     "pb_op_get_diagonal": [c_p, P_d],
     "pb_op_set_coefficient": [c_p, c_p, C.c_int],
     "pb_op_get_coefficient": [c_p, c_p, C.POINTER(C.c_int)],
+    "pb_op_set_mass": [c_p, c_p, C.c_double],
+    "pb_op_get_mass": [c_p, c_p, C.POINTER(C.c_double)],
     "pb_op_get_diagonal_vec": [c_p, c_p],
     "pb_op_destroy": [c_p],
     "pb_op_get_ownership_range": [c_p, P_i64, P_i64],

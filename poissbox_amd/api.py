@@ -391,6 +391,18 @@ class Mat:
         L.call("pb_op_get_coefficient", self.h, beta.h if beta is not None else None, C.byref(m))
         return m.value
 
+    def set_mass(self, m=None, s=0.0):
+        """VARCOEF: the mass term A = div(beta grad) - s m (m a Vec of the operator's grid, every
+        value finite and >= 0, copied; None: ones; s finite and >= 0, 0 switches the term off);
+        collective. A KSP whose A has the term on needs nullspace = 0."""
+        L.call("pb_op_set_mass", self.h, m.h if m is not None else None, float(s))
+
+    def mass(self, m=None):
+        """VARCOEF: s; m (a Vec), if given, receives the mass field (ones if none is set)."""
+        s = C.c_double()
+        L.call("pb_op_get_mass", self.h, m.h if m is not None else None, C.byref(s))
+        return s.value
+
     def diagonal_vec(self, v):
         """MatGetDiagonal into the Vec v (VARCOEF: the diagonal field; 7-point kinds: broadcast)."""
         L.call("pb_op_get_diagonal_vec", self.h, v.h)

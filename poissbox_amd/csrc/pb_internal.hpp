@@ -178,8 +178,14 @@ struct pb_op {
   double* beta_store = nullptr;
   double* beta = nullptr;
   int mean = PB_COEF_ARITHMETIC;
-  // counts pb_op_set_coefficient / pb_op_set_deltas: what a KSP derived from the operator (the
-  // variable Jacobi's reciprocal diagonal) is rebuilt by
+  // the mass term of pb_op_set_mass: A = div(beta grad) - q, q_c = mass_s * mass_c. mass: the owned
+  // copy of the caller's field (no ghost planes: q is point-local), nullptr = ones; the term is on
+  // iff mass_s != 0
+  double* mass = nullptr;
+  double mass_s = 0.0;
+  bool mass_on() const { return mass_s != 0.0; }
+  // counts pb_op_set_coefficient / pb_op_set_mass / pb_op_set_deltas: what a KSP derived from the
+  // operator (the variable Jacobi's reciprocal diagonal) is rebuilt by
   int64_t change = 0;
   int in_solve = 0;  // KSPs between pb_ksp_begin and pb_ksp_end with this operator as A or P
 };
@@ -325,14 +331,19 @@ int launch_star7_apply(pb_grid* g, const Star& s, const double* x, double* y,
                        const StencilPlanes& gp, int mode);
 // ---- the variable-coefficient operator (pb_varcoef.hip) ----
 // what a launch reads of a PB_OP_VARCOEF operator: the axis coefficients 1 / h_d^2, beta at local
-// plane 0 (its planes -1 and nzl are the operator's ghost planes) and the mean
+// plane 0 (its planes -1 and nzl are the operator's ghost planes), the mean and the mass term
+// q_c = ms * mass_c (mass == nullptr: q_c = ms; ms == 0: no term, mass is not read)
 struct VarCoef {
   double cx, cy, cz;
   const double* beta;
   int mean;
+  const double* mass = nullptr;
+  double ms = 0.0;
+  // the kernels' MASS: 0 none, 1 scalar, 2 field
+  int mass_kind() const { return ms == 0.0 ? 0 : (mass ? 2 : 1); }
 };
 inline VarCoef varcoef_of(const pb_op* op) {
-  return VarCoef{op->cx, op->cy, op->cz, op->beta, op->mean};
+  return VarCoef{op->cx, op->cy, op->cz, op->beta, op->mean, op->mass, op->mass_s};
 }
 // y = A x over the planes of `mode` (x's planes -1 / nzl by gp); dot: the per-block partial sums
 // of x . y into ctx->d_partials from block part_off on, *nblocks of them (else 0). Honours
@@ -345,8 +356,9 @@ int launch_varcoef_residual(pb_grid* g, const VarCoef& c, const double* x, const
                             double* res, const StencilPlanes& gp, const int* skip);
 // out = diag(A), or its reciprocal (what PCJacobi stores)
 int launch_varcoef_diag(pb_grid* g, const VarCoef& c, double* out, bool recip);
-// *count = the values of v, over all ranks, that are not finite and > 0 (collective, synchronous)
-int varcoef_count_bad(pb_grid* g, const double* v, double* count);
+// *count = the values of v, over all ranks, that are not finite and > 0 (zero_ok: >= 0)
+// (collective, synchronous)
+int varcoef_count_bad(pb_grid* g, const double* v, bool zero_ok, double* count);
 // z = dinv o r (the Jacobi PC of a variable P); exits at entry when *skip is set
 int launch_varcoef_jacobi(pb_grid* g, const double* dinv, const double* r, double* z,
                           const int* skip);

@@ -46,6 +46,7 @@ void mg_destroy(Mg* mg) {
   if (mg->agg) (void)hipFree(mg->agg);
   if (mg->pmem) (void)hipFree(mg->pmem);
   if (mg->vmem) (void)hipFree(mg->vmem);
+  if (mg->qmem) (void)hipFree(mg->qmem);
   delete mg;
 }
 

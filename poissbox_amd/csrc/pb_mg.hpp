@@ -55,6 +55,11 @@ struct MgLevel {
   const double* beta = nullptr;
   double* beta_own = nullptr;  // (below level 0: beta, writable)
   double* dinv = nullptr;
+  // the mass term of the coefficient operator on this level (pb_op_set_mass): q_0 = s * m,
+  // q_(l+1) the 8-child mean of q_l; point-local, no ghost planes. nullptr: none or the scalar qs
+  // (a scalar-only mass stays s on every level)
+  double* q = nullptr;
+  double qs = 0.0;
   Star vs;
   LevelPlan plan;         // this apply's
   double* cur = nullptr;  // this apply's pre-smoothed iterate, from the down leg to the up leg
@@ -129,6 +134,7 @@ struct Mg {
   int64_t coef_seen = -1;
   int mean = PB_COEF_ARITHMETIC;  // coef's at the last build
   double* vmem = nullptr;         // the levels' beta (below level 0) and dinv
+  double* qmem = nullptr;         // the levels' q, allocated by the first build with a mass field
 };
 
 // ---- the launchers (pb_mg.hip): one per pass, used by every path of the driver ----

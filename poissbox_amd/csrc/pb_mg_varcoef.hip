@@ -7,12 +7,15 @@
 //               0.125 (((b000 + b100) + (b010 + b110)) + ((b001 + b101) + (b011 + b111))), b_abc the
 //               fine cell (2I + a, 2J + b, 2K + c); c_d = 1 / (2^l h_d)^2 of the operator's deltas
 //   faces       g_n = c_d face(beta_n, beta_c) (vc_face, pb_device.hpp: the operator's own)
-//   dinv        1.0 / diag_c, diag_c = -(((((g_z- + g_y-) + g_x-) + g_x+) + g_y+) + g_z+)
+//   mass        the operator's q = s m (pb_op_set_mass): q_0 = s * m, q_(l+1) the 8-child mean of
+//               q_l as beta's; a scalar-only mass is s on every level; point-local, no ghost planes
+//   dinv        1.0 / diag_c, diag_c = -(((((g_z- + g_y-) + g_x-) + g_x+) + g_y+) + g_z+) - q_c
 //               (varcoef_diag_kernel), stored per level with its ghost planes
 //   half-sweep  nb = ((((g_z- x_z- + g_y- x_y-) + g_x- x_x-) + g_x+ x_x+) + g_y+ x_y+) + g_z+ x_z+,
 //               t = (b - nb) dinv, x = (1 - omega) x + omega t on the colour, red = (i + j + k) even;
 //               the zero-initialised first half-sweep has nb = 0.0 and x = 0.0 in the same formula
-//   residual    b - A x by the operator's own kernel (varcoef_kernel's RES form, pb_varcoef.hip)
+//   residual    b - A x by the operator's own kernel (varcoef_kernel's RES form, pb_varcoef.hip),
+//               A x = S6 - q x
 //
 // The half-sweeps: one thread owns an (i even, i + 1) pair of a row and marches over a chunk of
 // planes with the pairs of x and beta of planes k - 1, k, k + 1 in registers (each loaded once per
@@ -32,6 +35,8 @@ struct VcLevel {
   double cx, cy, cz;
   const double* beta;  // local plane 0; planes -1 and nzl in place
   const double* dinv;  // likewise
+  const double* q;     // the level's mass field (MASS = 2), qs the scalar mass (MASS = 1)
+  double qs;
 };
 
 __device__ __forceinline__ int vwrap(int v, int n) { return v < 0 ? v + n : (v >= n ? v - n : v); }
@@ -78,19 +83,24 @@ __device__ __forceinline__ Faces vc_faces(const VcLevel& c, const VcCol& q, int 
   f.zp = c.cz * vc_face<HARM>(d ? bp.y : bp.x, b0);
   return f;
 }
-__device__ __forceinline__ double faces_dinv(const Faces& f) {
+// q: the mass term at the point (MASS != 0)
+template <int MASS>
+__device__ __forceinline__ double faces_dinv(const Faces& f, double q) {
   double s = f.zm + f.ym;
   s = s + f.xm;
   s = s + f.xp;
   s = s + f.yp;
   s = s + f.zp;
-  return 1.0 / -s;
+  if constexpr (MASS != 0) return 1.0 / (-s - q);
+  else return 1.0 / -s;
 }
 
 // One half-sweep of `color` in place. lo / hi: x's planes -1 and nzl. ZERO: the zero-initialised
 // first half-sweep -- x is not read, the colour gets omega ((b - 0.0) dinv) and the other colour
-// 0.0 (a pair store). DST: dinv from the level's stored field, else from the six faces.
-template <int HARM, int ZERO, int DST>
+// 0.0 (a pair store). DST: dinv from the level's stored field, else from the six faces and the
+// mass term at the point (MASS: 0 none, 1 the scalar c.qs, 2 the field c.q; DST: 0, the stored
+// field holds it).
+template <int HARM, int ZERO, int DST, int MASS>
 __global__ __launch_bounds__(256) void vmg_half_kernel(MgGeo G, VcLevel c, double* x,
                                                        const double* __restrict__ b,
                                                        const double* lo, const double* hi,
@@ -125,7 +135,8 @@ __global__ __launch_bounds__(256) void vmg_half_kernel(MgGeo G, VcLevel c, doubl
     if constexpr (kFaces) f = vc_faces<HARM>(c, q, d, bm, bc, bp, c.beta + base);
     double dinv;
     if constexpr (DST) dinv = c.dinv[id];
-    else dinv = faces_dinv(f);
+    else if constexpr (MASS == 2) dinv = faces_dinv<2>(f, c.q[id]);
+    else dinv = faces_dinv<MASS>(f, c.qs);
     double nb = 0.0, xo = 0.0;
     if constexpr (!ZERO) {
       const double* xk = x + base;
@@ -244,7 +255,7 @@ static int vmg_chunk(const Mg* mg, int64_t cols, int64_t nzl, int64_t* nchunk_ou
 }
 
 static VcLevel vc_level(const MgLevel& L) {
-  return VcLevel{L.vs.cx, L.vs.cy, L.vs.cz, L.beta, L.dinv};
+  return VcLevel{L.vs.cx, L.vs.cy, L.vs.cz, L.beta, L.dinv, L.q, L.qs};
 }
 
 template <int HARM, int ZERO>
@@ -254,14 +265,15 @@ static void launch_half(Mg* mg, MgLevel& L, const double* lo, const double* hi, 
   int64_t nchunk = 1;
   const int kc = vmg_chunk(mg, cols, G.nzl, &nchunk);
   const dim3 grid(vmg_blocks(cols * nchunk)), block(256);
-  if (mg->tn.vc_dinv_stored)
-    hipLaunchKernelGGL((vmg_half_kernel<HARM, ZERO, 1>), grid, block, 0, mg->ctx->stream, G,
-                       vc_level(L), L.x, (const double*)L.b, lo, hi, mg->omega, color, kc,
-                       mg->skip);
-  else
-    hipLaunchKernelGGL((vmg_half_kernel<HARM, ZERO, 0>), grid, block, 0, mg->ctx->stream, G,
-                       vc_level(L), L.x, (const double*)L.b, lo, hi, mg->omega, color, kc,
-                       mg->skip);
+#define PB_VMG_HALF(DST_, MASS_)                                                                \
+  hipLaunchKernelGGL((vmg_half_kernel<HARM, ZERO, DST_, MASS_>), grid, block, 0, mg->ctx->stream, \
+                     G, vc_level(L), L.x, (const double*)L.b, lo, hi, mg->omega, color, kc,       \
+                     mg->skip)
+  if (mg->tn.vc_dinv_stored) PB_VMG_HALF(1, 0);
+  else if (L.q) PB_VMG_HALF(0, 2);
+  else if (L.qs != 0.0) PB_VMG_HALF(0, 1);
+  else PB_VMG_HALF(0, 0);
+#undef PB_VMG_HALF
 }
 
 int vmg_smooth(Mg* mg, MgLevel& L, int color, int mode) {
@@ -301,20 +313,41 @@ int vmg_smooth(Mg* mg, MgLevel& L, int color, int mode) {
   return PB_OK;
 }
 
+// what the operator's kernels read of a level: its q as the field with s = 1.0 (1.0 * q is exact)
+// or the scalar
+static VarCoef level_coef(const Mg* mg, const MgLevel& L) {
+  return VarCoef{L.vs.cx, L.vs.cy, L.vs.cz, L.beta, mg->mean, L.q, L.q ? 1.0 : L.qs};
+}
+
 int vmg_residual(Mg* mg, MgLevel& F, const double* x, double* res) {
   StencilPlanes gp = wrap_planes();  // one rank: x's wrap planes in place
   if (mg->ctx->split) {
     PB_TRY(level_ghosts(F, x, &gp.ghost_lo, &gp.ghost_hi));
     gp.wrap = false;
   }
-  const VarCoef c{F.vs.cx, F.vs.cy, F.vs.cz, F.beta, mg->mean};
+  const VarCoef c = level_coef(mg, F);
   ScopedTimer tm(mg->ctx, "vmg_residual");
   return launch_varcoef_residual(F.g, c, x, F.b, res, gp, mg->skip);
+}
+
+// q_0 = s * m
+__global__ __launch_bounds__(256) void vmg_mass_kernel(const double* __restrict__ m, double s,
+                                                       double* __restrict__ q, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    q[i] = s * m[i];
 }
 
 int vmg_build(Mg* mg) {
   const pb_op* C = mg->coef;
   mg->mean = C->mean;
+  const bool qfield = C->mass_on() && C->mass;
+  if (qfield && !mg->qmem) {
+    int64_t total = 0;
+    for (const MgLevel& lv : mg->lv) total += lv.g->nlocal;
+    if (hipMalloc(&mg->qmem, (size_t)total * sizeof(double)) != hipSuccess)
+      return set_error(PB_ERR_ALLOC, "multigrid level mass fields: out of device memory");
+  }
+  double* qp = mg->qmem;
   for (size_t l = 0; l < mg->lv.size(); ++l) {
     MgLevel& lv = mg->lv[l];
     pb_grid* g = lv.g;
@@ -332,7 +365,21 @@ int vmg_build(Mg* mg) {
                              lv.beta_own - g->plane, lv.beta_own + g->nlocal));
       lv.beta = lv.beta_own;
     }
-    const VarCoef c{lv.vs.cx, lv.vs.cy, lv.vs.cz, lv.beta, mg->mean};
+    lv.q = nullptr;
+    lv.qs = qfield ? 0.0 : C->mass_s;
+    if (qfield) {
+      lv.q = qp;
+      qp += g->nlocal;
+      if (l == 0)
+        hipLaunchKernelGGL(vmg_mass_kernel, dim3(vmg_blocks(g->nlocal)), dim3(256), 0,
+                           mg->ctx->stream, C->mass, C->mass_s, lv.q, g->nlocal);
+      else
+        hipLaunchKernelGGL(vmg_coarsen_kernel, dim3(vmg_blocks(g->nlocal)), dim3(256), 0,
+                           mg->ctx->stream, mg->lv[l - 1].geo(), (const double*)mg->lv[l - 1].q,
+                           lv.geo(), lv.q);
+      PB_HIP(hipGetLastError());
+    }
+    const VarCoef c = level_coef(mg, lv);
     PB_TRY(launch_varcoef_diag(g, c, lv.dinv, true));
     PB_TRY(halo_exchange_n(g, lv.dinv, lv.dinv + (g->nzl - 1) * g->plane, 1, lv.dinv - g->plane,
                            lv.dinv + g->nlocal));

@@ -128,7 +128,7 @@ int pb_op_set_coefficient(pb_op* op, const pb_vec* beta, int mean) {
   PB_CHECK_ARG(beta->grid == g, "vector/operator grid mismatch");
   // checked on the caller's vector, over all ranks, before anything of the operator changes
   double bad = 0.0;
-  PB_TRY(varcoef_count_bad(g, beta->d, &bad));
+  PB_TRY(varcoef_count_bad(g, beta->d, false, &bad));
   if (bad != 0.0)
     return set_error(PB_ERR_ARG, "coefficient field: %.0f values are not finite and > 0", bad);
   pb_ctx* ctx = g->ctx;
@@ -154,6 +154,56 @@ int pb_op_get_coefficient(const pb_op* op, pb_vec* beta, int* mean) {
     PB_SYNC(g->ctx, "pb_op_get_coefficient");
   }
   if (mean) *mean = op->mean;
+  return PB_OK;
+}
+
+int pb_op_set_mass(pb_op* op, const pb_vec* m, double s) {
+  PB_CHECK_ARG(op, "bad args");
+  PB_TRY(varcoef_only(op, "pb_op_set_mass"));
+  if (op->in_solve > 0)
+    return set_error(PB_ERR_STATE, "pb_op_set_mass inside a solve that holds the operator");
+  PB_CHECK_ARG(s >= 0.0 && s < INFINITY, "the mass factor s must be finite and >= 0");
+  pb_grid* g = op->grid;
+  if (!m) {
+    if (op->mass) {
+      PB_SYNC(g->ctx, "pb_op_set_mass");  // (launches that read the field)
+      field_free(op->mass);
+      op->mass = nullptr;
+    }
+  } else {
+    PB_CHECK_ARG(m->grid == g, "vector/operator grid mismatch");
+    // checked on the caller's vector, over all ranks, before anything of the operator changes
+    double bad = 0.0;
+    PB_TRY(varcoef_count_bad(g, m->d, true, &bad));
+    if (bad != 0.0)
+      return set_error(PB_ERR_ARG, "mass field: %.0f values are not finite and >= 0", bad);
+    const size_t bytes = (size_t)g->nlocal * sizeof(double);
+    if (!op->mass && field_alloc(&op->mass, bytes) != hipSuccess) {
+      op->mass = nullptr;
+      return set_error(PB_ERR_ALLOC, "mass field: out of device memory");
+    }
+    PB_HIP(hipMemcpyAsync(op->mass, m->d, bytes, hipMemcpyDeviceToDevice, g->ctx->stream));
+    PB_SYNC(g->ctx, "pb_op_set_mass");
+  }
+  op->mass_s = s;
+  ++op->change;
+  return PB_OK;
+}
+
+int pb_op_get_mass(const pb_op* op, pb_vec* m, double* s) {
+  PB_CHECK_ARG(op, "bad args");
+  PB_TRY(varcoef_only(op, "pb_op_get_mass"));
+  if (m) {
+    pb_grid* g = op->grid;
+    PB_CHECK_ARG(m->grid == g, "vector/operator grid mismatch");
+    if (op->mass)
+      PB_HIP(hipMemcpyAsync(m->d, op->mass, (size_t)g->nlocal * sizeof(double),
+                            hipMemcpyDeviceToDevice, g->ctx->stream));
+    else
+      PB_TRY(vec_fill(g->ctx, m->d, g->nlocal, 1.0));
+    PB_SYNC(g->ctx, "pb_op_get_mass");
+  }
+  if (s) *s = op->mass_s;
   return PB_OK;
 }
 
@@ -203,10 +253,11 @@ int pb_op_get_diagonal(const pb_op* op, double* diag) {
 
 int pb_op_destroy(pb_op* op) {
   if (!op) return PB_OK;
-  if (op->work || op->beta_store)
+  if (op->work || op->beta_store || op->mass)
     (void)wait_stream(op->grid->ctx, op->grid->ctx->stream, "pb_op_destroy");
   if (op->work) (void)hipFree(op->work);
   field_free(op->beta_store);
+  field_free(op->mass);
   delete op;
   return PB_OK;
 }

@@ -174,9 +174,21 @@ static int preonly_split_form(const pb_ksp* k) {
   return PB_OK;
 }
 
+// A with the mass term on (pb_op_set_mass) is nonsingular: the constant null space must not be
+// projected out of its solves. A alone is read: a mass in P or in the PC's coefficient operator
+// only makes a nonsingular preconditioner of a singular A
+static int mass_nullspace(const pb_ksp* k) {
+  if (k->A->mass_on() && k->opts.nullspace != 0)
+    return set_error(PB_ERR_STATE,
+                     "A has a mass term (pb_op_set_mass, s != 0) and is nonsingular: create the "
+                     "KSP with nullspace = 0");
+  return PB_OK;
+}
+
 int pb_ksp_begin(pb_ksp* k, const pb_vec* b, pb_vec* x) {
   PB_CHECK_ARG(k && b && x, "bad begin args");
   PB_TRY(preonly_split_form(k));
+  PB_TRY(mass_nullspace(k));
   pb_grid* g = k->A->grid;
   PB_CHECK_ARG(b->grid == g && x->grid == g, "vector/operator grid mismatch");
   pb_ctx* ctx = g->ctx;
@@ -336,6 +348,7 @@ int pb_ksp_end(pb_ksp* k, pb_ksp_result* res, double* history, int64_t cap) {
 int pb_ksp_solve(pb_ksp* k, const pb_vec* b, pb_vec* x, pb_ksp_result* res, double* history,
                  int64_t cap) {
   PB_CHECK_ARG(k, "ksp is NULL");
+  PB_TRY(mass_nullspace(k));
   ScopedTimer tm(k->A->grid->ctx, "KSPSolve");
   if (k->opts.ksp_type == PB_KSP_PREONLY) return solve_preonly(k, b, x, res);
   if (k->opts.guess_type != PB_GUESS_NONE) return solve_projected(k, b, x, res, history, cap);

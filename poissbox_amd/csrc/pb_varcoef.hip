@@ -49,13 +49,17 @@ __device__ __forceinline__ void vc_issue_rows(int kk, int nzl, int wrap, int64_t
 // needs no plane select. x's planes -1 / nzl: the wrap planes of x in place (g.wrap, one rank) or
 // the grid's ghost planes. parts != nullptr: the per-block partial sum of x . y (CG's p . Ap).
 // RES (the variable multigrid's residual pass, pb_mg_varcoef.hip): y = rb - A x instead of A x.
-template <int V, int TY, int HARM, int RES>
+// MASS (pb_op_set_mass): A x = S6 - q x with q = ms (1: the bytes of MASS = 0) or ms * mf at the
+// point (2: one more non-temporal row load, as rb's -- q is point-local, it does not go through
+// the z-queue and nothing of it is shared between points); 0: no term, the code without it.
+template <int V, int TY, int HARM, int RES, int MASS>
 __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, double cy, double cz,
                                                            const double* __restrict__ x,
                                                            const double* __restrict__ bt,
                                                            const double* __restrict__ ghost_lo,
                                                            const double* __restrict__ ghost_hi,
                                                            const double* __restrict__ rb,
+                                                           const double* __restrict__ mf, double ms,
                                                            double* __restrict__ y, double* parts,
                                                            const int* __restrict__ skip) {
   if (skip && *skip) return;  // device-side convergence flag (uniform)
@@ -168,8 +172,9 @@ __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, dou
 #pragma unroll
         for (int e = 1; e < V; ++e) fx[e] = cx * vc_face<HARM>(b1[t][e - 1], b1[t][e]);
         fx[V] = cx * vc_face<HARM>(br, b1[t][V - 1]);
-        double w[V], rbv[V];
+        double w[V], rbv[V], mv[V];
         if constexpr (RES) load_row_nt<V>(rb, rix(base + (int64_t)(j0 + t) * nx), rbv);
+        if constexpr (MASS == 2) load_row_nt<V>(mf, rix(base + (int64_t)(j0 + t) * nx), mv);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           const double xc = x1[t][e];
@@ -184,6 +189,8 @@ __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, dou
           s = s + fx[e + 1] * (xp - xc);
           s = s + fy[t + 1][e] * (yp - xc);
           s = s + fzp * (x2[t][e] - xc);
+          if constexpr (MASS == 2) s = s - (ms * mv[e]) * xc;
+          else if constexpr (MASS == 1) s = s - ms * xc;
           if constexpr (RES) w[e] = rbv[e] - s;
           else w[e] = s;
           fzm[t][e] = fzp;  // the face above plane k is the face below plane k + 1
@@ -200,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void varcoef_kernel(Geo g, double cx, dou
 }
 
 // rb != nullptr: y = rb - A x (no sums), exiting at entry on `skip` instead of ctx->op_skip
-template <int V, int TY, int HARM>
+template <int V, int TY, int HARM, int MASS>
 static int launch_varcoef_t(pb_grid* g, const VarCoef& c, const double* x, double* y,
                             const StencilPlanes& gp, int mode, bool dot, int part_off,
                             int* nblocks, const double* rb, const int* skip) {
@@ -217,25 +224,27 @@ static int launch_varcoef_t(pb_grid* g, const VarCoef& c, const double* x, doubl
     return set_error(PB_ERR_UNSUPPORTED, "varcoef grid of %lld blocks exceeds partials capacity",
                      (long long)nb);
   if (rb)
-    hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM, 1>), dim3((unsigned)nb), dim3(kThreads), 0,
-                       g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo, gp.ghost_hi,
-                       rb, y, nullptr, skip);
+    hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM, 1, MASS>), dim3((unsigned)nb), dim3(kThreads),
+                       0, g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo,
+                       gp.ghost_hi, rb, c.mass, c.ms, y, nullptr, skip);
   else
-    hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM, 0>), dim3((unsigned)nb), dim3(kThreads), 0,
-                       g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo, gp.ghost_hi,
-                       rb, y, dot ? g->ctx->d_partials + part_off : nullptr, g->ctx->op_skip);
+    hipLaunchKernelGGL((varcoef_kernel<V, TY, HARM, 0, MASS>), dim3((unsigned)nb), dim3(kThreads),
+                       0, g->ctx->stream, geo, c.cx, c.cy, c.cz, x, c.beta, gp.ghost_lo,
+                       gp.ghost_hi, rb, c.mass, c.ms, y,
+                       dot ? g->ctx->d_partials + part_off : nullptr, g->ctx->op_skip);
   PB_HIP(hipGetLastError());
   if (nblocks) *nblocks = dot ? (int)nb : 0;
   return PB_OK;
 }
 
-template <int HARM>
-static int launch_varcoef_m(pb_grid* g, const VarCoef& c, const double* x, double* y,
+template <int HARM, int MASS>
+static int launch_varcoef_k(pb_grid* g, const VarCoef& c, const double* x, double* y,
                             const StencilPlanes& gp, int mode, bool dot, int part_off,
-                            int* nblocks, const double* rb = nullptr, const int* skip = nullptr) {
+                            int* nblocks, const double* rb, const int* skip) {
   const int ty = pick_ty((int)g->n[1]);
-#define PB_VC(V_, TY_) \
-  return launch_varcoef_t<V_, TY_, HARM>(g, c, x, y, gp, mode, dot, part_off, nblocks, rb, skip)
+#define PB_VC(V_, TY_)                                                                         \
+  return launch_varcoef_t<V_, TY_, HARM, MASS>(g, c, x, y, gp, mode, dot, part_off, nblocks, rb, \
+                                               skip)
   if (g->n[0] % 2 == 0) {
     if (ty == 4) PB_VC(2, 4);
     if (ty == 2) PB_VC(2, 2);
@@ -245,6 +254,18 @@ static int launch_varcoef_m(pb_grid* g, const VarCoef& c, const double* x, doubl
   if (ty == 2) PB_VC(1, 2);
   PB_VC(1, 1);
 #undef PB_VC
+}
+
+// the mass off: MASS = 0, the instantiations without the term
+template <int HARM>
+static int launch_varcoef_m(pb_grid* g, const VarCoef& c, const double* x, double* y,
+                            const StencilPlanes& gp, int mode, bool dot, int part_off,
+                            int* nblocks, const double* rb = nullptr, const int* skip = nullptr) {
+  switch (c.mass_kind()) {
+    case 0: return launch_varcoef_k<HARM, 0>(g, c, x, y, gp, mode, dot, part_off, nblocks, rb, skip);
+    case 1: return launch_varcoef_k<HARM, 1>(g, c, x, y, gp, mode, dot, part_off, nblocks, rb, skip);
+    default: return launch_varcoef_k<HARM, 2>(g, c, x, y, gp, mode, dot, part_off, nblocks, rb, skip);
+  }
 }
 
 int launch_varcoef_apply(pb_grid* g, const VarCoef& c, const double* x, double* y,
@@ -263,18 +284,19 @@ int launch_varcoef_residual(pb_grid* g, const VarCoef& c, const double* x, const
 }
 
 // ---------------------------------------------------------------------------------------------
-// The diagonal -(((((g_z- + g_y-) + g_x-) + g_x+) + g_y+) + g_z+) (recip: 1.0 / it, what PCJacobi
-// stores), the check of a coefficient field and z = dinv o r. Setup and vector passes: grid-stride.
+// The diagonal -(((((g_z- + g_y-) + g_x-) + g_x+) + g_y+) + g_z+) - q, q the mass term by MASS
+// (recip: 1.0 / it, PCJacobi's), the check of a field and z = dinv o r. Grid-stride passes.
 // ---------------------------------------------------------------------------------------------
 static int vc_blocks(const pb_ctx* ctx, int64_t n) {
   const int64_t want = (n + 255) / 256, cap = (int64_t)ctx->num_cus * 8;
   return (int)std::max<int64_t>(1, std::min(want, cap));
 }
 
-template <int HARM>
+template <int HARM, int MASS>
 __global__ __launch_bounds__(256) void varcoef_diag_kernel(int nx, int ny, int64_t plane,
                                                            int64_t n, double cx, double cy,
                                                            double cz, const double* __restrict__ bt,
+                                                           const double* __restrict__ mf, double ms,
                                                            double* out, int recip) {
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < n;
        idx += (int64_t)gridDim.x * 256) {
@@ -294,42 +316,52 @@ __global__ __launch_bounds__(256) void varcoef_diag_kernel(int nx, int ny, int64
     s = s + gxp;
     s = s + gyp;
     s = s + gzp;
-    const double d = -s;
+    double d = -s;
+    if constexpr (MASS == 2) d = d - ms * mf[idx];
+    else if constexpr (MASS == 1) d = d - ms;
     out[idx] = recip ? 1.0 / d : d;
   }
 }
 
-int launch_varcoef_diag(pb_grid* g, const VarCoef& c, double* out, bool recip) {
+template <int HARM, int MASS>
+static void launch_varcoef_diag_t(pb_grid* g, const VarCoef& c, double* out, bool recip) {
   pb_ctx* ctx = g->ctx;
-  const int nb = vc_blocks(ctx, g->nlocal);
-  if (c.mean == PB_COEF_HARMONIC)
-    hipLaunchKernelGGL(varcoef_diag_kernel<1>, dim3(nb), dim3(256), 0, ctx->stream, (int)g->n[0],
-                       (int)g->n[1], g->plane, g->nlocal, c.cx, c.cy, c.cz, c.beta, out,
-                       recip ? 1 : 0);
-  else
-    hipLaunchKernelGGL(varcoef_diag_kernel<0>, dim3(nb), dim3(256), 0, ctx->stream, (int)g->n[0],
-                       (int)g->n[1], g->plane, g->nlocal, c.cx, c.cy, c.cz, c.beta, out,
-                       recip ? 1 : 0);
+  hipLaunchKernelGGL((varcoef_diag_kernel<HARM, MASS>), dim3(vc_blocks(ctx, g->nlocal)), dim3(256),
+                     0, ctx->stream, (int)g->n[0], (int)g->n[1], g->plane, g->nlocal, c.cx, c.cy,
+                     c.cz, c.beta, c.mass, c.ms, out, recip ? 1 : 0);
+}
+
+int launch_varcoef_diag(pb_grid* g, const VarCoef& c, double* out, bool recip) {
+  const int mk = c.mass_kind();
+  if (c.mean == PB_COEF_HARMONIC) {
+    if (mk == 0) launch_varcoef_diag_t<1, 0>(g, c, out, recip);
+    else if (mk == 1) launch_varcoef_diag_t<1, 1>(g, c, out, recip);
+    else launch_varcoef_diag_t<1, 2>(g, c, out, recip);
+  } else {
+    if (mk == 0) launch_varcoef_diag_t<0, 0>(g, c, out, recip);
+    else if (mk == 1) launch_varcoef_diag_t<0, 1>(g, c, out, recip);
+    else launch_varcoef_diag_t<0, 2>(g, c, out, recip);
+  }
   PB_HIP(hipGetLastError());
   return PB_OK;
 }
 
-// the number of values that are not finite and > 0, per block
+// the number of values that are not finite and > 0 (zero_ok: >= 0, a mass field), per block
 __global__ __launch_bounds__(256) void varcoef_check_kernel(const double* __restrict__ v, int64_t n,
-                                                            double* parts) {
+                                                            int zero_ok, double* parts) {
   double acc[1] = {0.0};
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const double a = v[i];
-    if (!(a > 0.0 && a < INFINITY)) acc[0] += 1.0;
+    if (!((zero_ok ? a >= 0.0 : a > 0.0) && a < INFINITY)) acc[0] += 1.0;
   }
   block_partials<1>(acc, parts);
 }
 
-int varcoef_count_bad(pb_grid* g, const double* v, double* count) {
+int varcoef_count_bad(pb_grid* g, const double* v, bool zero_ok, double* count) {
   pb_ctx* ctx = g->ctx;
   const int nb = vc_blocks(ctx, g->nlocal);
   hipLaunchKernelGGL(varcoef_check_kernel, dim3(nb), dim3(256), 0, ctx->stream, v, g->nlocal,
-                     ctx->d_partials);
+                     zero_ok ? 1 : 0, ctx->d_partials);
   PB_HIP(hipGetLastError());
   double* dsum = ctx->d_scalars + 8;
   PB_TRY(reduce_partials(ctx, ctx->d_partials, nb, 1, dsum));

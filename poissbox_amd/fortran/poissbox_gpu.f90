@@ -140,6 +140,8 @@ module poissbox_gpu
   ! PB_OP_VARCOEF: the coefficient field and the diagonal as a vector (op, beta, diag: the handles
   ! of a Mat / Vec, their component h)
   public :: c_pb_op_set_coefficient, c_pb_op_get_coefficient, c_pb_op_get_diagonal_vec
+  ! its mass term A = div(beta grad) - s m (m: a Vec's handle or c_null_ptr for ones)
+  public :: c_pb_op_set_mass, c_pb_op_get_mass
 
   interface PoissboxAllreduceSum  ! ≙ MPI_Allreduce(..., MPI_SUM, MPI_COMM_WORLD)
      module procedure allreduce_sum_int, allreduce_sum_real
@@ -200,6 +202,16 @@ module poissbox_gpu
        import :: c_int, c_ptr
        type(c_ptr), value :: op, beta
        integer(c_int) :: mean
+     end function
+     integer(c_int) function c_pb_op_set_mass(op, m, s) bind(C, name="pb_op_set_mass")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: op, m
+       real(c_double), value :: s
+     end function
+     integer(c_int) function c_pb_op_get_mass(op, m, s) bind(C, name="pb_op_get_mass")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: op, m
+       real(c_double) :: s
      end function
      integer(c_int) function c_pb_op_get_diagonal_vec(op, diag) &
           bind(C, name="pb_op_get_diagonal_vec")
