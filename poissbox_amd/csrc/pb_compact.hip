@@ -291,10 +291,8 @@ static int launch_line(pb_ctx* ctx, int kind, int stagger, double dx, int64_t n,
 
 // direction d of an n0*n1*n2 box (the owned slab: n2 = nzl; or a y-slab with complete z-lines)
 static LineMap dir_map(const int64_t b[3], int d) {
-  const int64_t nx = b[0], ny = b[1];
-  if (d == 0) return LineMap{ny, nx, nx * ny, 1};
-  if (d == 1) return LineMap{nx, 1, nx * ny, nx};
-  return LineMap{nx * ny, 1, 0, nx * ny};
+  const LineGeo q = line_geo(b, d);  // line l = outer * ninner + inner
+  return LineMap{q.ninner, q.li, q.lo, q.es};
 }
 
 enum { K_GRAD = 0, K_INTERP = 1 };
@@ -316,24 +314,7 @@ static int line3(pb_grid* g, int d, int kind, int stagger, double dx, const doub
 // Z steps on a split grid run on y-slabs (complete z-lines; pb_compact_dist.hip transposes):
 // same line kernels, same per-line operation order => bit-identical to one rank. Scratch for
 // them: 4 y-slab fields + the transpose aux space.
-static int64_t zsplit_len(const pb_grid* g) {
-  return grid_split(g) ? 4 * yslab_len(g) + yslab_aux_len(g) : 0;
-}
-
-struct ZSplit {
-  YSlabPlan p;
-  double* y[4];
-  int64_t b[3];
-};
-static int zsplit_begin(pb_grid* g, double* ws, ZSplit* z) {
-  const int64_t L = yslab_len(g);
-  for (int i = 0; i < 4; ++i) z->y[i] = ws + i * L;
-  PB_TRY(yslab_begin(g, ws + 4 * L, &z->p));
-  z->b[0] = g->n[0];
-  z->b[1] = z->p.ny_me;
-  z->b[2] = g->n[2];
-  return PB_OK;
-}
+static int64_t zsplit_len(const pb_grid* g) { return grid_split(g) ? yslab_fields_len(g, 4) : 0; }
 
 // src/compact_schemes.f90:42-88 grad; scratch 5N (+ zsplit_len)
 static int grad3(pb_grid* g, const double dx[3], const double* f, double* df1, double* df2,
@@ -344,8 +325,8 @@ static int grad3(pb_grid* g, const double dx[3], const double* f, double* df1, d
     PB_TRY(line3(g, 2, K_INTERP, -1, 0.0, f, dff1));    // :61
     PB_TRY(line3(g, 2, K_GRAD, -1, dx[2], f, dff3));    // :63  (dff2 = dff1, :62)
   } else {
-    ZSplit z;
-    PB_TRY(zsplit_begin(g, ws + 5 * N, &z));
+    YSlabFields z;
+    PB_TRY(yslab_fields_begin(g, ws + 5 * N, 4, &z));
     PB_TRY(yslab_to(g, z.p, f, z.y[0]));
     PB_TRY(line_box(g->ctx, z.b, 2, K_INTERP, -1, 0.0, z.y[0], z.y[1]));
     PB_TRY(line_box(g->ctx, z.b, 2, K_GRAD, -1, dx[2], z.y[0], z.y[2]));
@@ -379,8 +360,8 @@ static int div3(pb_grid* g, const double dx[3], const double* f1, const double* 
     PB_TRY(line3(g, 2, K_GRAD, +1, dx[2], dff3, out, nullptr, dfc));  // :249-250
     return PB_OK;
   }
-  ZSplit z;
-  PB_TRY(zsplit_begin(g, ws + 6 * N, &z));
+  YSlabFields z;
+  PB_TRY(yslab_fields_begin(g, ws + 6 * N, 4, &z));
   PB_TRY(yslab_to(g, z.p, dff1, z.y[0]));
   PB_TRY(yslab_to(g, z.p, dff2, z.y[1]));
   PB_TRY(yslab_to(g, z.p, dff3, z.y[2]));
@@ -547,8 +528,8 @@ int pb_compact_interp(pb_grid* g, int stagger, const pb_vec* f, pb_vec* fi) {
   if (!grid_split(g)) {
     rc = line3(g, 2, K_INTERP, stagger, 0.0, f->d, ws);             // :238
   } else {  // the Z step on y-slabs
-    ZSplit z;
-    rc = zsplit_begin(g, ws + 2 * N, &z);
+    YSlabFields z;
+    rc = yslab_fields_begin(g, ws + 2 * N, 4, &z);
     if (!rc) rc = yslab_to(g, z.p, f->d, z.y[0]);
     if (!rc) rc = line_box(g->ctx, z.b, 2, K_INTERP, stagger, 0.0, z.y[0], z.y[1]);
     if (!rc) rc = yslab_from(g, z.p, z.y[1], ws);

@@ -188,6 +188,18 @@ int yslab_begin(pb_grid* g, double* aux, YSlabPlan* p) {
   return PB_OK;
 }
 
+int64_t yslab_fields_len(const pb_grid* g, int nf) { return nf * yslab_len(g) + yslab_aux_len(g); }
+
+int yslab_fields_begin(pb_grid* g, double* ws, int nf, YSlabFields* z) {
+  const int64_t L = yslab_len(g);
+  for (int i = 0; i < nf; ++i) z->y[i] = ws + i * L;
+  PB_TRY(yslab_begin(g, ws + nf * L, &z->p));
+  z->b[0] = g->n[0];
+  z->b[1] = z->p.ny_me;
+  z->b[2] = g->n[2];
+  return PB_OK;
+}
+
 bool yslab_blocked(const YSlabPlan& p) {
   const int64_t n = p.nyl.empty() ? 0 : p.nyl[0];
   if (n <= 0 || (n & (n - 1))) return false;
@@ -223,16 +235,14 @@ int yslab_from(pb_grid* g, const YSlabPlan& p, const double* fy, double* f) {
 }
 
 // y-slab fields fy, uy, vy and the transpose aux space
-int64_t compact_dist_work_len(const pb_grid* g) { return 3 * yslab_len(g) + yslab_aux_len(g); }
+int64_t compact_dist_work_len(const pb_grid* g) { return yslab_fields_len(g, 3); }
 
 int compact_dist_pass_z(pb_grid* g, double h, const double* f, double* u, double* v, double* work,
                         YSlabPlan* plan_out, bool* blocked) {
-  const int64_t ny_slab = yslab_len(g);
-  double* fy = work;
-  double* uy = fy + ny_slab;
-  double* vy = uy + ny_slab;
-  YSlabPlan p;
-  PB_TRY(yslab_begin(g, vy + ny_slab, &p));
+  YSlabFields z;
+  PB_TRY(yslab_fields_begin(g, work, 3, &z));
+  const YSlabPlan& p = z.p;
+  double *fy = z.y[0], *uy = z.y[1], *vy = z.y[2];
   // CG on a split grid (CgFuse): p is formed by the pack; the y-slab Z pass must not form it
   // again, so the fusion is hidden from the passes until the transposes are done (the X pass
   // takes p . w)
@@ -244,8 +254,7 @@ int compact_dist_pass_z(pb_grid* g, double h, const double* f, double* u, double
   } hide{g->ctx, cf};
   g->ctx->cg_fuse = nullptr;
   PB_TRY(yslab_to(g, p, f, fy, cf));
-  const int64_t dy[3] = {g->n[0], p.ny_me, g->n[2]};
-  PB_TRY(compact_pass_z(g->ctx, dy, h, fy, uy, vy));
+  PB_TRY(compact_pass_z(g->ctx, z.b, h, fy, uy, vy));
   if (blocked) *blocked = false;
   if (plan_out && blocked && yslab_blocked(p)) {
     // received straight into u, v (nlocal doubles each) in the all-to-all layout

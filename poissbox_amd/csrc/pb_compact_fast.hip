@@ -246,84 +246,54 @@ static bool reg_lines(int64_t n) {
   return lines_ok && compact_lines_supported(n);
 }
 
+// One pass on the LDS-PCR kernel along `axis` of the box d: out[t.out] += (op t.op, whole or the
+// half at t.half) in[t.in] over the terms t; out1 == nullptr: one output.
+static int pcr_pass(pb_ctx* ctx, const int64_t d[3], int axis, double h, const Term* terms,
+                    int nterms, const double* in0, const double* in1, double* out0, double* out1) {
+  const LineGeo q = line_geo(d, axis);
+  if (q.n > kTile) return set_error(PB_ERR_UNSUPPORTED, "compact fast path: n > %d", kTile);
+  FastPass p{};
+  p.n = (int)q.n;
+  p.layout = q.layout;
+  p.ninner = q.ninner;
+  p.nouter = q.nouter;
+  p.li = q.li;
+  p.lo = q.lo;
+  p.es = q.es;
+  p.nterms = nterms;
+  for (int t = 0; t < nterms; ++t) p.term[t] = terms[t];
+  p.ops[0] = make_op(0, q.n, h);
+  p.ops[1] = make_op(1, q.n, h);
+  p.in[0] = in0;
+  p.in[1] = in1;
+  p.out[0] = out0;
+  p.out[1] = out1;
+  p.nout = out1 ? 2 : 1;
+  return launch_pass(ctx, p);
+}
+
 // Z: u = Jz f, v = Lz f
 int compact_pass_z(pb_ctx* ctx, const int64_t d[3], double h, const double* f, double* u, double* v) {
-  const int64_t nx = d[0], ny = d[1], nz = d[2];
-  if (nz > kTile) return set_error(PB_ERR_UNSUPPORTED, "compact fast path: n > %d", kTile);
-  if (reg_lines(nz)) return compact_lines_pass(ctx, d, 2, h, f, nullptr, u, v);
-  FastPass p{};  // lines along k; tile = consecutive i for fixed j
-  p.n = (int)nz;
-  p.layout = 0;
-  p.ninner = (int)nx;
-  p.nouter = (int)ny;
-  p.li = 1;
-  p.lo = nx;
-  p.es = nx * ny;
-  p.nterms = 2;
-  p.term[0] = Term{0, 0, 0};
-  p.term[1] = Term{1, 0, 1};
-  p.ops[0] = make_op(0, nz, h);
-  p.ops[1] = make_op(1, nz, h);
-  p.in[0] = f;
-  p.out[0] = u;
-  p.out[1] = v;
-  p.nout = 2;
-  return launch_pass(ctx, p);
+  if (reg_lines(d[2])) return compact_lines_pass(ctx, d, 2, h, f, nullptr, u, v);
+  const Term t[2] = {{0, 0, 0}, {1, 0, 1}};
+  return pcr_pass(ctx, d, 2, h, t, 2, f, nullptr, u, v);
 }
 
 // Y: s = Jy u, t = Ly u + Jy v
 int compact_pass_y(pb_ctx* ctx, const int64_t d[3], double h, const double* u, const double* v,
                    double* s_, double* t, const YSlabPlan* blk_in) {
-  const int64_t nx = d[0], ny = d[1], nz = d[2];
-  if (ny > kTile) return set_error(PB_ERR_UNSUPPORTED, "compact fast path: n > %d", kTile);
-  if (reg_lines(ny)) return compact_lines_pass(ctx, d, 1, h, u, v, s_, t, blk_in);
+  if (reg_lines(d[1])) return compact_lines_pass(ctx, d, 1, h, u, v, s_, t, blk_in);
   if (blk_in) return set_error(PB_ERR_ARG, "compact Y pass: blocked input needs the line solves");
-  FastPass p{};  // lines along j; tile = consecutive i for fixed k
-  p.n = (int)ny;
-  p.layout = 0;
-  p.ninner = (int)nx;
-  p.nouter = (int)nz;
-  p.li = 1;
-  p.lo = nx * ny;
-  p.es = nx;
-  p.nterms = 3;
-  p.term[0] = Term{0, 0, 0};  // s = Jy u
-  p.term[1] = Term{1, 0, 1};  // t = Ly u
-  p.term[2] = Term{0, 1, 1};  //   + Jy v
-  p.ops[0] = make_op(0, ny, h);
-  p.ops[1] = make_op(1, ny, h);
-  p.in[0] = u;
-  p.in[1] = v;
-  p.out[0] = s_;
-  p.out[1] = t;
-  p.nout = 2;
-  return launch_pass(ctx, p);
+  const Term tm[3] = {{0, 0, 0}, {1, 0, 1}, {0, 1, 1}};
+  return pcr_pass(ctx, d, 1, h, tm, 3, u, v, s_, t);
 }
 
 // X: out = Lx s + Jx t
 int compact_pass_x(pb_ctx* ctx, const int64_t d[3], double h, const double* s_, const double* t,
                    double* out) {
-  const int64_t nx = d[0], ny = d[1], nz = d[2];
-  if (nx > kTile) return set_error(PB_ERR_UNSUPPORTED, "compact fast path: n > %d", kTile);
-  if (reg_lines(nx)) return compact_lines_pass(ctx, d, 0, h, s_, t, out, nullptr);
-  FastPass p{};  // lines along i (contiguous); tile = consecutive j for fixed k
-  p.n = (int)nx;
-  p.layout = 1;
-  p.ninner = (int)ny;
-  p.nouter = (int)nz;
-  p.li = nx;
-  p.lo = nx * ny;
-  p.es = 1;
-  p.nterms = 2;
-  p.term[0] = Term{1, 0, 0};  // out = Lx s
-  p.term[1] = Term{0, 1, 0};  //     + Jx t
-  p.ops[0] = make_op(0, nx, h);
-  p.ops[1] = make_op(1, nx, h);
-  p.in[0] = s_;
-  p.in[1] = t;
-  p.out[0] = out;
-  p.nout = 1;
-  return launch_pass(ctx, p);
+  if (reg_lines(d[0])) return compact_lines_pass(ctx, d, 0, h, s_, t, out, nullptr);
+  const Term tm[2] = {{1, 0, 0}, {0, 1, 0}};
+  return pcr_pass(ctx, d, 0, h, tm, 2, s_, t, out, nullptr);
 }
 
 // One half-operator pass (grad / div / interp, pb_compact_ops.hip) on the LDS-PCR kernel:
@@ -331,37 +301,15 @@ int compact_pass_x(pb_ctx* ctx, const int64_t d[3], double h, const double* s_, 
 // An X pass (lines contiguous, layout 1) may run in place: a block reads its whole lines first.
 int compact_half_pass_pcr(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
                           const HalfPass& a) {
-  const int64_t nx = d[0], ny = d[1], nz = d[2];
-  const int64_t n = d[axis];
-  if (n > kTile) return set_error(PB_ERR_UNSUPPORTED, "compact fast path: n > %d", kTile);
-  FastPass p{};
-  p.n = (int)n;
-  if (axis == 2) {  // lines along k; tile = consecutive i for fixed j
-    p.layout = 0, p.ninner = (int)nx, p.nouter = (int)ny;
-    p.li = 1, p.lo = nx, p.es = nx * ny;
-  } else if (axis == 1) {  // lines along j; tile = consecutive i for fixed k
-    p.layout = 0, p.ninner = (int)nx, p.nouter = (int)nz;
-    p.li = 1, p.lo = nx * ny, p.es = nx;
-  } else {  // lines along i (contiguous); tile = consecutive j for fixed k
-    p.layout = 1, p.ninner = (int)ny, p.nouter = (int)nz;
-    p.li = nx, p.lo = nx * ny, p.es = 1;
-  }
-  p.ops[0] = make_op(0, n, h);
-  p.ops[1] = make_op(1, n, h);
-  p.in[0] = a.in0;
-  p.in[1] = a.in1;
-  p.out[0] = a.out0;
-  p.out[1] = a.out1;
-  p.nout = a.out1 ? 2 : 1;
-  p.nterms = 1;
-  p.term[0] = Term{a.k0, 0, 0, stagger};
-  if (a.in1) p.term[p.nterms++] = Term{a.k1, 1, 0, stagger};
-  if (a.out1) p.term[p.nterms++] = Term{a.k1, 0, 1, stagger};
-  return launch_pass(ctx, p);
+  Term t[3] = {{a.k0, 0, 0, stagger}};
+  int nt = 1;
+  if (a.in1) t[nt++] = Term{a.k1, 1, 0, stagger};
+  if (a.out1) t[nt++] = Term{a.k1, 0, 1, stagger};
+  return pcr_pass(ctx, d, axis, h, t, nt, a.in0, a.in1, a.out0, a.out1);
 }
 
 // work doubles: 4 N (u, v, s, t) on one rank; on N ranks also the y-slab fields and the
-// transpose staging (compact_dist.cpp)
+// transpose staging (pb_compact_dist.hip)
 int64_t compact_fast_work_len(const pb_grid* g) {
   if (!g->ctx->split) return 4 * g->nlocal;
   return 4 * g->nlocal + compact_dist_work_len(g);

@@ -389,41 +389,16 @@ bool compact_cg_fusable_split(const pb_grid* g) {
 }
 
 bool compact_lines_supported(int64_t n) {
-  if (n % 64) return false;
-  const int64_t C = n / 64;
-  return C == 1 || C == 2 || C == 3 || C == 4 || C == 6 || C == 8 || C == 12 || C == 16;
-}
-
-template <int C, int LAYOUT, int PASS, class K, int V, bool CGP = false>
-static int launch_lines_v(pb_ctx* ctx, LinePass& p, int64_t nouter) {
-  p.TL = K::TL;
-  p.P = Lds<C>::LP;
-  p.ntiles_inner = (p.ninner + K::TL - 1) / K::TL;
-  p.nouter = (int)nouter;
-  const int64_t ntiles = (int64_t)p.ntiles_inner * nouter;
-  const size_t lds = (size_t)K::TL * Lds<C>::LP * sizeof(double);
-  auto kern = compact_lines_kernel<C, LAYOUT, PASS, K, V, CGP>;
-  static int occ = 0;
-  if (!occ) {
-    PB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    PB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, K::NT, lds));
-    if (occ < 1) occ = 1;
-  }
-  int64_t nblocks = K::PF ? (int64_t)occ * ctx->num_cus : ntiles;
-  if (nblocks > ntiles) nblocks = ntiles;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(K::NT), lds, ctx->stream, p);
-  PB_HIP(hipGetLastError());
-  return PB_OK;
+  return for_line_c(n, [](auto) { return (int)PB_OK; }) == PB_OK;
 }
 
 // 16-byte pairs when the contiguous direction has even length (always for LAYOUT 1, n = 64*C)
 template <int C, int LAYOUT, int PASS, class K>
 static int launch_lines_k(pb_ctx* ctx, LinePass& p, int64_t nouter) {
   if (LAYOUT == 1 || (p.ninner % 2 == 0 && p.li == 1 && p.lo % 2 == 0 && p.es % 2 == 0 &&
-                      ((uintptr_t)p.in0 & 15) == 0 && ((uintptr_t)p.out0 & 15) == 0))
-    return launch_lines_v<C, LAYOUT, PASS, K, 2>(ctx, p, nouter);
-  return launch_lines_v<C, LAYOUT, PASS, K, 1>(ctx, p, nouter);
+                      aligned16(p.in0, p.out0)))
+    return launch_lines_tiled<compact_lines_kernel<C, LAYOUT, PASS, K, 2>, K, C>(ctx, p, nouter);
+  return launch_lines_tiled<compact_lines_kernel<C, LAYOUT, PASS, K, 1>, K, C>(ctx, p, nouter);
 }
 
 // Launch shapes (measured at 512^3, profiles/r01/tune_compact*.jsonl): strided passes use 16-line
@@ -442,25 +417,19 @@ static int launch_lines_c(pb_ctx* ctx, LinePass& p, int64_t nouter) {
 
 template <int LAYOUT, int PASS>
 static int launch_lines(pb_ctx* ctx, LinePass& p, int64_t n, int64_t nouter) {
-  switch (n / 64) {
-    case 1: return launch_lines_c<1, LAYOUT, PASS>(ctx, p, nouter);
-    case 2: return launch_lines_c<2, LAYOUT, PASS>(ctx, p, nouter);
-    case 3: return launch_lines_c<3, LAYOUT, PASS>(ctx, p, nouter);
-    case 4: return launch_lines_c<4, LAYOUT, PASS>(ctx, p, nouter);
-    case 6: return launch_lines_c<6, LAYOUT, PASS>(ctx, p, nouter);
-    case 8: return launch_lines_c<8, LAYOUT, PASS>(ctx, p, nouter);
-    case 12: return launch_lines_c<12, LAYOUT, PASS>(ctx, p, nouter);
-    case 16: return launch_lines_c<16, LAYOUT, PASS>(ctx, p, nouter);
-  }
-  return set_error(PB_ERR_UNSUPPORTED, "compact line solver: n = %lld", (long long)n);
+  if (!compact_lines_supported(n))
+    return set_error(PB_ERR_UNSUPPORTED, "compact line solver: n = %lld", (long long)n);
+  return for_line_c(n, [&](auto c) {
+    return launch_lines_c<decltype(c)::value, LAYOUT, PASS>(ctx, p, nouter);
+  });
 }
 
 // One pass of the factorised Laplacian with register line solves. axis: 2 = Z, 1 = Y, 0 = X.
 int compact_lines_pass(pb_ctx* ctx, const int64_t dims[3], int axis, double h, const double* in0,
                        const double* in1, double* out0, double* out1, const YSlabPlan* blk_in) {
-  const int64_t nx = dims[0], ny = dims[1], nz = dims[2];
-  const int64_t n = axis == 2 ? nz : (axis == 1 ? ny : nx);
-  const int C = (int)(n / 64);
+  const LineGeo q = line_geo(dims, axis);
+  const int64_t nx = dims[0], nz = dims[2];
+  const int C = (int)(q.n / 64);
   static const char* names[3] = {"compact_lines_x", "compact_lines_y", "compact_lines_z"};
   ScopedTimer tm(ctx, names[axis]);
   LinePass p{};
@@ -474,39 +443,33 @@ int compact_lines_pass(pb_ctx* ctx, const int64_t dims[3], int axis, double h, c
   p.out1 = out1;
   p.J = make_line_op(0, C, h);
   p.L = make_line_op(1, C, h);
+  p.li = q.li;
+  p.lo = q.lo;
+  p.es = q.es;
+  p.ninner = q.ninner;
   if (axis == 2) {
-    p.li = 1;
-    p.lo = nx;
-    p.es = nx * ny;
-    p.ninner = (int)nx;
     CgFuse* cf = ctx->cg_fuse;
-    if (cf && cf->z && C <= 8 && nx % 2 == 0 && ((uintptr_t)cf->z & 15) == 0 &&
-        ((uintptr_t)out0 & 15) == 0) {
+    if (cf && cf->z && C <= 8 && nx % 2 == 0 && aligned16(cf->z, out0)) {
       // CG's p formed by the Z pass from z and p_old (CgFuse); in0 is not read
       p.in0 = cf->z;
       p.in1 = cf->p_old;
       p.p_out = cf->p_out;
       p.st = cf->st;
       p.first = cf->first;
-      int rc = PB_ERR_UNSUPPORTED;
-      switch (C) {
-        case 1: rc = launch_lines_v<1, 0, 0, LineCfg<16, 16, 1>, 2, true>(ctx, p, ny); break;
-        case 2: rc = launch_lines_v<2, 0, 0, LineCfg<16, 16, 1>, 2, true>(ctx, p, ny); break;
-        case 3: rc = launch_lines_v<3, 0, 0, LineCfg<16, 16, 1>, 2, true>(ctx, p, ny); break;
-        case 4: rc = launch_lines_v<4, 0, 0, LineCfg<16, 16, 1>, 2, true>(ctx, p, ny); break;
-        case 6: rc = launch_lines_v<6, 0, 0, LineCfg<16, 16, 1>, 2, true>(ctx, p, ny); break;
-        case 8: rc = launch_lines_v<8, 0, 0, LineCfg<16, 16, 1>, 2, true>(ctx, p, ny); break;
-      }
+      const int rc = for_line_c(q.n, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
+        using K = LineCfg<16, 16, 1>;
+        if constexpr (CC <= 8)  // (the CGP kernels exist up to C = 8)
+          return launch_lines_tiled<compact_lines_kernel<CC, 0, 0, K, 2, true>, K, CC>(ctx, p, q.nouter);
+        else
+          return (int)PB_ERR_UNSUPPORTED;
+      });
       if (rc == PB_OK) cf->fused_z = true;
       return rc;
     }
-    return launch_lines<0, 0>(ctx, p, n, ny);
+    return launch_lines<0, 0>(ctx, p, q.n, q.nouter);
   }
   if (axis == 1) {
-    p.li = 1;
-    p.lo = nx * ny;
-    p.es = nx;
-    p.ninner = (int)nx;
     if (blk_in) {  // row (kl, j) at block j >> k, row kl * nyl + (j & (nyl - 1))
       const int64_t nyl = blk_in->nyl[0];
       int sh = 0;
@@ -519,26 +482,15 @@ int compact_lines_pass(pb_ctx* ctx, const int64_t dims[3], int axis, double h, c
         p.alt0 = blk_in->alt0;
         p.alt1 = blk_in->alt1;
       }
-      return launch_lines<0, 4>(ctx, p, n, nz);
+      return launch_lines<0, 4>(ctx, p, q.n, q.nouter);
     }
-    return launch_lines<0, 1>(ctx, p, n, nz);
+    return launch_lines<0, 1>(ctx, p, q.n, q.nouter);
   }
   if (blk_in) return set_error(PB_ERR_ARG, "compact lines: blocked input on the Y pass only");
-  p.li = nx;
-  p.lo = nx * ny;
-  p.es = 1;
-  p.ninner = (int)ny;
-  switch (C) {
-    case 1: return launch_x_direct<1>(ctx, p, ny * nz);
-    case 2: return launch_x_direct<2>(ctx, p, ny * nz);
-    case 3: return launch_x_direct<3>(ctx, p, ny * nz);
-    case 4: return launch_x_direct<4>(ctx, p, ny * nz);
-    case 6: return launch_x_direct<6>(ctx, p, ny * nz);
-    case 8: return launch_x_direct<8>(ctx, p, ny * nz);
-    case 12: return launch_x_direct<12>(ctx, p, ny * nz);
-    case 16: return launch_x_direct<16>(ctx, p, ny * nz);
-  }
-  return set_error(PB_ERR_UNSUPPORTED, "compact lines: X extent %lld", (long long)nx);
+  if (!compact_lines_supported(nx))
+    return set_error(PB_ERR_UNSUPPORTED, "compact lines: X extent %lld", (long long)nx);
+  const int64_t nlines = (int64_t)q.ninner * q.nouter;
+  return for_line_c(nx, [&](auto c) { return launch_x_direct<decltype(c)::value>(ctx, p, nlines); });
 }
 
 // Batched periodic (alpha, 1, alpha) solve, in place, n = 64*C points per line: contiguous
@@ -555,19 +507,11 @@ int lines_solve_batched(pb_ctx* ctx, int64_t n, int64_t nbatch, int64_t line_str
   p.in0 = d;
   p.out0 = d;
   p.J = make_solve_op(alpha, C);
-  const bool al16 = ((uintptr_t)d & 15) == 0;
-  if (elem_stride == 1 && line_stride % 2 == 0 && al16 && line_stride >= n) {
+  if (elem_stride == 1 && line_stride % 2 == 0 && aligned16(d) && line_stride >= n) {
     p.li = line_stride;
-    switch (C) {
-      case 1: return launch_solve_direct<1>(ctx, p, nbatch);
-      case 2: return launch_solve_direct<2>(ctx, p, nbatch);
-      case 3: return launch_solve_direct<3>(ctx, p, nbatch);
-      case 4: return launch_solve_direct<4>(ctx, p, nbatch);
-      case 6: return launch_solve_direct<6>(ctx, p, nbatch);
-      case 8: return launch_solve_direct<8>(ctx, p, nbatch);
-      case 12: return launch_solve_direct<12>(ctx, p, nbatch);
-      case 16: return launch_solve_direct<16>(ctx, p, nbatch);
-    }
+    return for_line_c(n, [&](auto c) {
+      return launch_solve_direct<decltype(c)::value>(ctx, p, nbatch);
+    });
   }
   if (line_stride == 1 && elem_stride >= nbatch) {
     p.li = 1;

@@ -1,15 +1,42 @@
 // pb_compact_lines.hpp -- device pieces of the register-resident compact line solves, shared by
 // the factorised Laplacian's passes (pb_compact_lines.hip) and the half-operator passes of grad /
 // div / interp (pb_compact_ops.hip): the per-lane explicit RHS, the periodic (alpha, 1, alpha)
-// solve, and the LDS tile transpose with its global <-> LDS copies. Include after
+// solve, and the LDS tile transpose with its global <-> LDS copies; and the host pieces both
+// launch sides share: the list of line lengths (for_line_c), the 16-byte alignment test
+// (aligned16) and the tiled passes' launcher (launch_lines_tiled). Include after
 // pb_internal.hpp / pb_device.hpp; the arithmetic is written for contraction, so the including
 // file sets `#pragma clang fp contract(fast)` first (as this header does for itself).
 #pragma once
 #include <cmath>
+#include <cstdint>
+#include <type_traits>
 
 #pragma clang fp contract(fast)
 
 namespace pb {
+
+// The line lengths the register solves are compiled for, n = 64*C: f(integral_constant<int, C>)
+// for n's C, PB_ERR_UNSUPPORTED (no error text set) for any other n. The only copy of the list.
+template <class F>
+static int for_line_c(int64_t n, F&& f) {
+  switch (n % 64 ? 0 : n / 64) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+  }
+  return PB_ERR_UNSUPPORTED;
+}
+
+// every pointer on a 16-byte boundary (the 16-byte moves' condition; nullptr counts as aligned)
+template <class... P>
+static bool aligned16(const P*... p) {
+  return ((((uintptr_t)p & 15) == 0) && ...);
+}
 
 struct LineOp {
   double a, b, sign;  // explicit 4-point RHS (src/compact_schemes.f90:332-372)
@@ -366,6 +393,32 @@ template <int TL_, int NW_, int PF_>
 struct LineCfg {
   static constexpr int TL = TL_, NW = NW_, PF = PF_, NT = 64 * NW_, LPW = TL_ / NW_;
 };
+
+// Launch the tiled pass kernel Kern (launch shape K, lines of 64*C points) over p's tiles: the
+// dynamic-LDS attribute and the occupancy are taken once per kernel (`occ` is one per
+// instantiation, i.e. per Kern); persistent shapes (K::PF) get occupancy x CUs blocks at most,
+// the others one block per tile.
+template <auto Kern, class K, int C>
+static int launch_lines_tiled(pb_ctx* ctx, LinePass& p, int64_t nouter) {
+  p.TL = K::TL;
+  p.P = Lds<C>::LP;
+  p.ntiles_inner = (p.ninner + K::TL - 1) / K::TL;
+  p.nouter = (int)nouter;
+  const int64_t ntiles = (int64_t)p.ntiles_inner * nouter;
+  const size_t lds = (size_t)K::TL * Lds<C>::LP * sizeof(double);
+  static int occ = 0;
+  if (!occ) {
+    PB_HIP(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds));
+    PB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, Kern, K::NT, lds));
+    if (occ < 1) occ = 1;
+  }
+  int64_t nblocks = K::PF ? (int64_t)occ * ctx->num_cus : ntiles;
+  if (nblocks > ntiles) nblocks = ntiles;
+  hipLaunchKernelGGL(Kern, dim3((unsigned)nblocks), dim3(K::NT), lds, ctx->stream, p);
+  PB_HIP(hipGetLastError());
+  return PB_OK;
+}
 
 // wave-private LDS strips: order the wave's own LDS writes and reads without a block barrier
 __device__ __forceinline__ void wave_sync() {

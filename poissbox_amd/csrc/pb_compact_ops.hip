@@ -194,29 +194,6 @@ __global__ __launch_bounds__(256) void half_x_direct(LinePass p, int64_t nlines)
   }
 }
 
-template <int C, int SHAPE, class K, int V>
-static int launch_half_v(pb_ctx* ctx, LinePass& p, int64_t nouter) {
-  p.TL = K::TL;
-  p.P = Lds<C>::LP;
-  p.ntiles_inner = (p.ninner + K::TL - 1) / K::TL;
-  p.nouter = (int)nouter;
-  const int64_t ntiles = (int64_t)p.ntiles_inner * nouter;
-  const size_t lds = (size_t)K::TL * Lds<C>::LP * sizeof(double);
-  auto kern = half_lines_kernel<C, SHAPE, K, V>;
-  static int occ = 0;
-  if (!occ) {
-    PB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    PB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, K::NT, lds));
-    if (occ < 1) occ = 1;
-  }
-  int64_t nblocks = K::PF ? (int64_t)occ * ctx->num_cus : ntiles;
-  if (nblocks > ntiles) nblocks = ntiles;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(K::NT), lds, ctx->stream, p);
-  PB_HIP(hipGetLastError());
-  return PB_OK;
-}
-
 // the Laplacian's launch shapes (pb_compact_lines.hip): 16-line tiles, persistent with prefetch,
 // up to C = 8; 8-line tiles, one per block, above (LDS). 16-byte row moves when the rows are even.
 // (2 -> 1 at C = 8 with 8-byte moves, i.e. an odd x extent: the 1024-thread block's 128 VGPRs
@@ -225,23 +202,17 @@ template <int C, int SHAPE>
 static int launch_half_c(pb_ctx* ctx, LinePass& p, int64_t nouter, bool pairs) {
   using K = std::conditional_t<(C <= 8), LineCfg<16, 16, 1>, LineCfg<8, 8, 0>>;
   using K1 = std::conditional_t<(C == 8 && SHAPE == 2), LineCfg<8, 8, 0>, K>;
-  if (pairs) return launch_half_v<C, SHAPE, K, 2>(ctx, p, nouter);
-  return launch_half_v<C, SHAPE, K1, 1>(ctx, p, nouter);
+  if (pairs) return launch_lines_tiled<half_lines_kernel<C, SHAPE, K, 2>, K, C>(ctx, p, nouter);
+  return launch_lines_tiled<half_lines_kernel<C, SHAPE, K1, 1>, K1, C>(ctx, p, nouter);
 }
 
 template <int SHAPE>
-static int launch_half(pb_ctx* ctx, LinePass& p, int C, int64_t nouter, bool pairs) {
-  switch (C) {
-    case 1: return launch_half_c<1, SHAPE>(ctx, p, nouter, pairs);
-    case 2: return launch_half_c<2, SHAPE>(ctx, p, nouter, pairs);
-    case 3: return launch_half_c<3, SHAPE>(ctx, p, nouter, pairs);
-    case 4: return launch_half_c<4, SHAPE>(ctx, p, nouter, pairs);
-    case 6: return launch_half_c<6, SHAPE>(ctx, p, nouter, pairs);
-    case 8: return launch_half_c<8, SHAPE>(ctx, p, nouter, pairs);
-    case 12: return launch_half_c<12, SHAPE>(ctx, p, nouter, pairs);
-    case 16: return launch_half_c<16, SHAPE>(ctx, p, nouter, pairs);
-  }
-  return set_error(PB_ERR_UNSUPPORTED, "compact half pass: n = %d", 64 * C);
+static int launch_half(pb_ctx* ctx, LinePass& p, int64_t n, int64_t nouter, bool pairs) {
+  if (!compact_lines_supported(n))
+    return set_error(PB_ERR_UNSUPPORTED, "compact half pass: n = %d", (int)n);
+  return for_line_c(n, [&](auto c) {
+    return launch_half_c<decltype(c)::value, SHAPE>(ctx, p, nouter, pairs);
+  });
 }
 
 template <int C>
@@ -252,16 +223,13 @@ static int launch_half_x(pb_ctx* ctx, LinePass& p, int64_t nlines) {
   return PB_OK;
 }
 
-static bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 int compact_half_pass(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
                       const HalfPass& a) {
-  const int64_t nx = d[0], ny = d[1], nz = d[2];
-  const int64_t n = d[axis];
+  const LineGeo q = line_geo(d, axis);
   if (a.in1 && a.out1) return set_error(PB_ERR_ARG, "compact half pass: 2 -> 2");
-  if (!(tune("compact_lines", 1) && compact_lines_supported(n)))
+  if (!(tune("compact_lines", 1) && compact_lines_supported(q.n)))
     return compact_half_pass_pcr(ctx, d, axis, h, stagger, a);
-  const int C = (int)(n / 64);
+  const int C = (int)(q.n / 64);
   static const char* names[3] = {"compact_half_x", "compact_half_y", "compact_half_z"};
   ScopedTimer tm(ctx, names[axis]);
   LinePass p{};
@@ -275,37 +243,20 @@ int compact_half_pass(pb_ctx* ctx, const int64_t d[3], int axis, double h, int s
   p.L = make_line_op(a.k1, C, h);
   if (axis == 0) {
     // (the chains above only have 1 -> 1 X passes; the 16-byte moves need aligned fields)
-    if (a.in1 || a.out1 || !al16(a.in0) || !al16(a.out0))
+    if (a.in1 || a.out1 || !aligned16(a.in0, a.out0))
       return compact_half_pass_pcr(ctx, d, axis, h, stagger, a);
-    switch (C) {
-      case 1: return launch_half_x<1>(ctx, p, ny * nz);
-      case 2: return launch_half_x<2>(ctx, p, ny * nz);
-      case 3: return launch_half_x<3>(ctx, p, ny * nz);
-      case 4: return launch_half_x<4>(ctx, p, ny * nz);
-      case 6: return launch_half_x<6>(ctx, p, ny * nz);
-      case 8: return launch_half_x<8>(ctx, p, ny * nz);
-      case 12: return launch_half_x<12>(ctx, p, ny * nz);
-      case 16: return launch_half_x<16>(ctx, p, ny * nz);
-    }
-    return set_error(PB_ERR_UNSUPPORTED, "compact half pass: X extent %lld", (long long)nx);
+    const int64_t nlines = (int64_t)q.ninner * q.nouter;
+    return for_line_c(q.n, [&](auto c) { return launch_half_x<decltype(c)::value>(ctx, p, nlines); });
   }
-  p.li = 1;
-  p.ninner = (int)nx;
-  int64_t nouter;
-  if (axis == 2) {
-    p.lo = nx;
-    p.es = nx * ny;
-    nouter = ny;
-  } else {
-    p.lo = nx * ny;
-    p.es = nx;
-    nouter = nz;
-  }
-  const bool pairs = nx % 2 == 0 && al16(a.in0) && al16(a.out0) && (!a.in1 || al16(a.in1)) &&
-                     (!a.out1 || al16(a.out1));
-  if (a.in1) return launch_half<2>(ctx, p, C, nouter, pairs);
-  if (a.out1) return launch_half<1>(ctx, p, C, nouter, pairs);
-  return launch_half<0>(ctx, p, C, nouter, pairs);
+  p.li = q.li;
+  p.lo = q.lo;
+  p.es = q.es;
+  p.ninner = q.ninner;
+  // (an absent in1 / out1 is nullptr: aligned)
+  const bool pairs = d[0] % 2 == 0 && aligned16(a.in0, a.out0, a.in1, a.out1);
+  if (a.in1) return launch_half<2>(ctx, p, q.n, q.nouter, pairs);
+  if (a.out1) return launch_half<1>(ctx, p, q.n, q.nouter, pairs);
+  return launch_half<0>(ctx, p, q.n, q.nouter, pairs);
 }
 
 namespace {
@@ -313,22 +264,7 @@ namespace {
 // Z passes on a split grid run on y-slabs (complete z-lines): plain pack / all-to-all / unpack
 // transposes around the same line kernels on the same whole lines, so every line's arithmetic is
 // the one-rank arithmetic. Scratch: three y-slab fields and the transpose staging.
-int64_t ops_zsplit_len(const pb_grid* g) { return grid_split(g) ? compact_dist_work_len(g) : 0; }
-
-struct ZSlabs {
-  YSlabPlan p;
-  double* y[3];
-  int64_t b[3];
-};
-int zslabs_begin(pb_grid* g, double* ws, ZSlabs* z) {
-  const int64_t L = yslab_len(g);
-  for (int i = 0; i < 3; ++i) z->y[i] = ws + i * L;
-  PB_TRY(yslab_begin(g, ws + 3 * L, &z->p));
-  z->b[0] = g->n[0];
-  z->b[1] = z->p.ny_me;
-  z->b[2] = g->n[2];
-  return PB_OK;
-}
+int64_t ops_zsplit_len(const pb_grid* g) { return grid_split(g) ? yslab_fields_len(g, 3) : 0; }
 
 // the Z pass `a` of a chain: in place on one rank, on y-slabs on a split grid
 int half_pass_z(pb_grid* g, double h, int stagger, const HalfPass& a, double* zws) {
@@ -336,8 +272,8 @@ int half_pass_z(pb_grid* g, double h, int stagger, const HalfPass& a, double* zw
     const int64_t d[3] = {g->n[0], g->n[1], g->nzl};
     return compact_half_pass(g->ctx, d, 2, h, stagger, a);
   }
-  ZSlabs z;
-  PB_TRY(zslabs_begin(g, zws, &z));
+  YSlabFields z;
+  PB_TRY(yslab_fields_begin(g, zws, 3, &z));
   HalfPass ay = a;
   PB_TRY(yslab_to(g, z.p, a.in0, z.y[0]));
   ay.in0 = z.y[0];

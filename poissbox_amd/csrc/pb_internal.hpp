@@ -570,9 +570,6 @@ bool cg_sr1_supported(const pb_grid* g);
 int launch_cg_sr1(pb_grid* g, const Star& s, const double* r, const double* p_old, double* p_new,
                   double* r_out, const Fold& f, double* parts_out, int* nblocks);
 
-// ---- compact fast path + generic CG (pb_compact_fast.hip) ----
-int64_t compact_fast_work_len(const pb_grid* g);
-int compact_lapl_fast(pb_grid* g, const double dx[3], const double* f, double* out, double* work);
 // integer user setting from the environment (the PB_* variables INTEGRATION.md lists), dflt when
 // unset
 inline int env_int(const char* name, int dflt) {
@@ -599,48 +596,33 @@ inline hipError_t field_alloc(T** p, size_t bytes) {
   return field_alloc(reinterpret_cast<void**>(p), bytes);
 }
 
-// ---- register-resident line solves (pb_compact_lines.hip) ----
+// ---- compact schemes: the factorised fast path (pb_compact_fast.hip, LDS PCR), its register
+// line solves (pb_compact_lines.hip), the half-operator passes of grad / div / interp
+// (pb_compact_ops.hip) and the z-slab <-> y-slab transposes (pb_compact_dist.hip) ----
+// The lines along `axis` of a box d = (nx, ny, nz), x fastest: n points per line, element e of
+// (outer, inner line) at outer*lo + inner*li + e*es, a tile = consecutive inner lines of one outer.
+// layout 0: lines run across rows (li == 1: Z, Y); 1: lines contiguous (es == 1: X). The one
+// statement of this mapping: FastPass, LinePass and the reference-order LineMap are filled from it.
+struct LineGeo {
+  int64_t n;
+  int ninner, nouter;
+  int64_t li, lo, es;
+  int layout;
+};
+inline LineGeo line_geo(const int64_t d[3], int axis) {
+  const int64_t nx = d[0], ny = d[1], nz = d[2];
+  if (axis == 2) return LineGeo{nz, (int)nx, (int)ny, 1, nx, nx * ny, 0};  // inner i, outer j
+  if (axis == 1) return LineGeo{ny, (int)nx, (int)nz, 1, nx * ny, nx, 0};  // inner i, outer k
+  return LineGeo{nx, (int)ny, (int)nz, nx, nx * ny, 1, 1};                 // inner j, outer k
+}
+int64_t compact_fast_work_len(const pb_grid* g);
+int compact_lapl_fast(pb_grid* g, const double dx[3], const double* f, double* out, double* work);
+// register line solves: n = 64*C for the C of for_line_c (pb_compact_lines.hpp)
 bool compact_lines_supported(int64_t n);
 bool compact_cg_fusable(const pb_grid* g);  // CgFuse applies to the compact operator on g
 bool compact_cg_fusable_split(const pb_grid* g);  // ... on a split grid (pack + X pass)
-struct YSlabPlan;
-// blk_in (Y pass of a decomposed grid): in0 / in1 are the all-to-all receive buffers in their
-// blocked layout (yslab_blocked), not z-slab fields
-int compact_lines_pass(pb_ctx* ctx, const int64_t dims[3], int axis, double h, const double* in0,
-                       const double* in1, double* out0, double* out1,
-                       const YSlabPlan* blk_in = nullptr);
-// batched periodic (alpha,1,alpha) solve in registers (n = 64*C); PB_ERR_UNSUPPORTED otherwise
-int lines_solve_batched(pb_ctx* ctx, int64_t n, int64_t nbatch, int64_t line_stride,
-                        int64_t elem_stride, double alpha, double* d);
-// the three passes of the factorised compact Laplacian on a box with complete lines
-int compact_pass_z(pb_ctx* ctx, const int64_t d[3], double h, const double* f, double* u, double* v);
-int compact_pass_y(pb_ctx* ctx, const int64_t d[3], double h, const double* u, const double* v,
-                   double* s, double* t, const YSlabPlan* blk_in = nullptr);
-int compact_pass_x(pb_ctx* ctx, const int64_t d[3], double h, const double* s, const double* t,
-                   double* out);
-// ---- half-operator line passes: the factorised grad / div / interp (pb_compact_ops.hip) ----
-// out0 = H(k0) in0 [+ H(k1) in1], optionally out1 = H(k1) in0 (never both); H(0) = interp_1d,
-// H(1) = grad_1d (h), every H applied once at the call's stagger along `axis` of the box d
-struct HalfPass {
-  int k0 = 0, k1 = 0;
-  const double* in0 = nullptr;
-  const double* in1 = nullptr;
-  double* out0 = nullptr;
-  double* out1 = nullptr;
-};
-// register line solves where n = 64*C supports them, else the LDS-PCR kernel
-int compact_half_pass(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
-                      const HalfPass& a);
-int compact_half_pass_pcr(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
-                          const HalfPass& a);
-// ---- multi-rank Z pass: z-slab <-> y-slab all-to-all transposes (compact_dist.cpp) ----
-int64_t compact_dist_work_len(const pb_grid* g);
-// plan_out != nullptr: on equal 2^k-row y-slabs u, v are left in the all-to-all layout (the plan
-// in *plan_out, *blocked = true) for a Y pass that reads them so; otherwise unpacked as z-slabs
-int compact_dist_pass_z(pb_grid* g, double h, const double* f, double* u, double* v, double* work,
-                        YSlabPlan* plan_out = nullptr, bool* blocked = nullptr);
 // z-slab <-> y-slab transposes (rank r holds rows [j0_r, j0_r + nyl_r) of every plane: complete
-// z-lines) for line operations along z on a split grid; pb_compact_dist.hip
+// z-lines) for line operations along z on a split grid
 struct YSlabPlan {
   std::vector<int64_t> k0, nzl, j0, nyl, zc, yc;
   int64_t ny_me = 0, ny_slab = 0;  // this rank's y rows; doubles of one y-slab field
@@ -663,7 +645,15 @@ struct YSlabPlan {
 int64_t yslab_len(const pb_grid* g);
 int64_t yslab_aux_len(const pb_grid* g);
 int yslab_begin(pb_grid* g, double* aux, YSlabPlan* p);  // aux: yslab_aux_len doubles
-struct CgFuse;
+// a Z step on a split grid: nf <= 4 y-slab fields y[0 .. nf) at ws, the transpose staging behind
+// them (yslab_fields_len doubles in all), the plan and the y-slab's box b (complete z-lines)
+struct YSlabFields {
+  YSlabPlan p;
+  double* y[4];
+  int64_t b[3];
+};
+int64_t yslab_fields_len(const pb_grid* g, int nf);
+int yslab_fields_begin(pb_grid* g, double* ws, int nf, YSlabFields* z);
 // cf (CG on a split grid): the pack forms CG's p from cf->z and p_old = f in place (sets
 // cf->fused_z)
 int yslab_to(pb_grid* g, const YSlabPlan& p, const double* f, double* fy, CgFuse* cf = nullptr);
@@ -675,6 +665,42 @@ int yslab_from(pb_grid* g, const YSlabPlan& p, const double* fy, double* f);
 // skip_self: the rank's own block is already in place (YSlabPlan::self_direct), not copied
 int alltoallv_device(pb_ctx* ctx, const double* send, const int64_t* scount, double* recv,
                      const int64_t* rcount, bool skip_self = false);
+// multi-rank Z pass of the fast Laplacian; work: compact_dist_work_len doubles.
+// plan_out != nullptr: on equal 2^k-row y-slabs u, v are left in the all-to-all layout (the plan
+// in *plan_out, *blocked = true) for a Y pass that reads them so; otherwise unpacked as z-slabs
+int64_t compact_dist_work_len(const pb_grid* g);
+int compact_dist_pass_z(pb_grid* g, double h, const double* f, double* u, double* v, double* work,
+                        YSlabPlan* plan_out = nullptr, bool* blocked = nullptr);
+// one pass of the factorised Laplacian with register line solves (axis: 2 = Z, 1 = Y, 0 = X).
+// blk_in (Y pass of a decomposed grid): in0 / in1 are the all-to-all receive buffers in their
+// blocked layout (yslab_blocked), not z-slab fields
+int compact_lines_pass(pb_ctx* ctx, const int64_t dims[3], int axis, double h, const double* in0,
+                       const double* in1, double* out0, double* out1,
+                       const YSlabPlan* blk_in = nullptr);
+// batched periodic (alpha,1,alpha) solve in registers (n = 64*C); PB_ERR_UNSUPPORTED otherwise
+int lines_solve_batched(pb_ctx* ctx, int64_t n, int64_t nbatch, int64_t line_stride,
+                        int64_t elem_stride, double alpha, double* d);
+// the three passes of the factorised compact Laplacian on a box with complete lines
+int compact_pass_z(pb_ctx* ctx, const int64_t d[3], double h, const double* f, double* u, double* v);
+int compact_pass_y(pb_ctx* ctx, const int64_t d[3], double h, const double* u, const double* v,
+                   double* s, double* t, const YSlabPlan* blk_in = nullptr);
+int compact_pass_x(pb_ctx* ctx, const int64_t d[3], double h, const double* s, const double* t,
+                   double* out);
+// half-operator line passes (the factorised grad / div / interp): out0 = H(k0) in0 [+ H(k1) in1],
+// optionally out1 = H(k1) in0 (never both); H(0) = interp_1d, H(1) = grad_1d (h), every H applied
+// once at the call's stagger along `axis` of the box d
+struct HalfPass {
+  int k0 = 0, k1 = 0;
+  const double* in0 = nullptr;
+  const double* in1 = nullptr;
+  double* out0 = nullptr;
+  double* out1 = nullptr;
+};
+// register line solves where n = 64*C supports them, else the LDS-PCR kernel
+int compact_half_pass(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
+                      const HalfPass& a);
+int compact_half_pass_pcr(pb_ctx* ctx, const int64_t d[3], int axis, double h, int stagger,
+                          const HalfPass& a);
 // Config-5 iteration fusions (compact A with a stored-z preconditioner, one rank, register line
 // solves): the compact operator's Z pass forms p = (dinv z - mu) + beta/beta_old p_old from its
 // tile loads and stores p (cg_gen_p_kernel's arithmetic, bit-identical), and its X pass takes the
