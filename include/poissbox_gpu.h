@@ -271,6 +271,33 @@ int pb_op_get_mass(const pb_op* op, pb_vec* m, double* s);
 /* ≙ MatGetDiagonal: diag_c above (with the mass term) for PB_OP_VARCOEF, the constant diagonal broadcast for
  * PB_OP_STAR7 / PB_OP_ASSEMBLED27 (PB_ERR_UNSUPPORTED for PB_OP_COMPACT). */
 int pb_op_get_diagonal_vec(const pb_op* op, pb_vec* diag);
+/* MAC-grid (staggered) gradient, projection and divergence of PB_OP_VARCOEF and PB_OP_STAR7
+ * (beta = 1): the operators G (cell to face) and D (face to cell) with D G = A to rounding, the two
+ * parts of a projection step around the solve. A face field is three cell-indexed vectors of the
+ * operator's grid; u_d(c) lives on the face between cell c and cell c + e_d (the plus face). All
+ * axes periodic. With r_d = 1.0 / h_d from the operator's deltas (one rounded division), face() the
+ * operator's mean above, and every product, sum and quotient rounded:
+ *   G_d(c) = (r_d * face(beta_(c+e_d), beta_c)) * (p_(c+e_d) - p_c)      pb_op_mac_grad
+ *   u_d(c) <- u_d(c) - (s * G_d(c))                                      pb_op_mac_project, in place
+ *   D(c)   = s * ((((ux(c) - ux(c-ex)) * r_x) + ((uy(c) - uy(c-ey)) * r_y))
+ *                 + ((uz(c) - uz(c-ez)) * r_z))                          pb_op_mac_div
+ * On PB_OP_STAR7 G_d(c) = r_d * (p_(c+e_d) - p_c), the bits of a PB_OP_VARCOEF with beta = 1 under
+ * either mean. The operator's mass term is no part of G: it is ignored. Because G uses the
+ * operator's own face coefficients (the same mean, beta and deltas) and D is the adjoint difference,
+ * a field projected with the solved p is discretely divergence-free to the solve's residual.
+ * The projection step of a variable-density flow (beta = 1 / rho, pb_op_set_coefficient):
+ *   pb_op_mac_div(A, 1 / dt, ustar, b);        b = (1/dt) div u*
+ *   pb_ksp_solve(ksp, b, p);                   div(beta grad p) = b
+ *   pb_op_mac_project(A, p, dt, ustar);        u = u* - dt beta_f grad p
+ * Collective (split grids: one halo exchange of p for grad / project, of uz for div, none of u in
+ * project). They only read the operator and may be called between pb_ksp_begin and pb_ksp_end.
+ * Stream ordered like pb_op_apply. grad: 16 B read + 24 B written per DoF (PB_OP_STAR7: 8 + 24),
+ * project 64 B/DoF (56), div 24 + 8. PB_ERR_UNSUPPORTED for PB_OP_COMPACT and PB_OP_ASSEMBLED27;
+ * PB_ERR_ARG for a vector of another grid, three components that are not distinct vectors, p among
+ * g / u, out among u, or a non-finite s. An error leaves every output untouched. */
+int pb_op_mac_grad(const pb_op* op, const pb_vec* p, pb_vec* const g[3]);           /* g_d = G_d(p)    */
+int pb_op_mac_project(const pb_op* op, const pb_vec* p, double s, pb_vec* const u[3]); /* u_d -= s G_d(p) */
+int pb_op_mac_div(const pb_op* op, double s, const pb_vec* const u[3], pb_vec* out);   /* out = s D(u)    */
 int pb_op_destroy(pb_op* op);
 /* ≙ MatGetOwnershipRange / VecGetOwnershipRange (src/example.f90:137-147): global row range
  * [first, next) owned by this rank (rank-contiguous natural order of the z-slab split). */

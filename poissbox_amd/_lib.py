@@ -118,6 +118,9 @@ _SIGS = {
     "pb_op_set_mass": [c_p, c_p, C.c_double],
     "pb_op_get_mass": [c_p, c_p, C.POINTER(C.c_double)],
     "pb_op_get_diagonal_vec": [c_p, c_p],
+    "pb_op_mac_grad": [c_p, c_p, C.POINTER(c_p)],
+    "pb_op_mac_project": [c_p, c_p, c_d, C.POINTER(c_p)],
+    "pb_op_mac_div": [c_p, c_d, C.POINTER(c_p), c_p],
     "pb_op_destroy": [c_p],
     "pb_op_get_ownership_range": [c_p, P_i64, P_i64],
     "pb_vec_get_ownership_range": [c_p, P_i64, P_i64],

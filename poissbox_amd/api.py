@@ -408,6 +408,27 @@ class Mat:
         L.call("pb_op_get_diagonal_vec", self.h, v.h)
         return v
 
+    # MAC-grid gradient, projection and divergence (STAR7, VARCOEF; include/poissbox_gpu.h): a
+    # face field is a sequence of three Vecs, component d on the plus face along axis d
+    @staticmethod
+    def _vec3(v3):
+        if len(v3) != 3:
+            raise ValueError("a face field is three Vecs")
+        return (C.c_void_p * 3)(*[v.h.value for v in v3])
+
+    def mac_grad(self, p, g3):
+        """g3[d] = G_d(p), the operator's own face flux: (r_d face(beta)) (p_+ - p_c); collective."""
+        L.call("pb_op_mac_grad", self.h, p.h, self._vec3(g3))
+
+    def mac_project(self, p, s, u3):
+        """u3[d] -= s G_d(p) in place (the projection's correction, s = dt); collective."""
+        L.call("pb_op_mac_project", self.h, p.h, float(s), self._vec3(u3))
+
+    def mac_div(self, u3, out, s=1.0):
+        """out = s D(u3), the adjoint difference of mac_grad (the projection's right-hand side,
+        s = 1 / dt): D G = A to rounding; collective."""
+        L.call("pb_op_mac_div", self.h, float(s), self._vec3(u3), out.h)
+
     def destroy(self):
         if self.h:
             L.call("pb_op_destroy", self.h)

@@ -362,6 +362,26 @@ int varcoef_count_bad(pb_grid* g, const double* v, bool zero_ok, double* count);
 // z = dinv o r (the Jacobi PC of a variable P); exits at entry when *skip is set
 int launch_varcoef_jacobi(pb_grid* g, const double* dinv, const double* r, double* z,
                           const int* skip);
+// ---- the MAC-grid gradient, projection and divergence of the 7-point operators (pb_mac.hip) ----
+// what a launch reads of the operator: r_d = 1.0 / h_d, beta at local plane 0 with the operator's
+// ghost planes around it (nullptr: PB_OP_STAR7, beta = 1) and the mean. The mass term is no part
+// of G
+struct MacCoef {
+  double rx, ry, rz;
+  const double* beta;
+  int mean;
+};
+inline MacCoef mac_coef_of(const pb_op* op) {
+  return MacCoef{1.0 / op->deltas[0], 1.0 / op->deltas[1], 1.0 / op->deltas[2],
+                 op->kind == PB_OP_VARCOEF ? op->beta : nullptr, op->mean};
+}
+// u_d = G_d(p), or (project) u_d = u_d - (s G_d(p)) in place, over the planes of `mode`; p's plane
+// nzl by gp (the wrap plane in place, or gp.ghost_hi)
+int launch_mac_grad(pb_grid* g, const MacCoef& c, const double* p, double s, double* const u[3],
+                    bool project, const StencilPlanes& gp, int mode);
+// out = s D(u) over the planes of `mode`; uz's plane -1 by gp (the wrap plane, or gp.ghost_lo)
+int launch_mac_div(pb_grid* g, const MacCoef& c, double s, const double* const u[3], double* out,
+                   const StencilPlanes& gp, int mode);
 // assembled P (pb_assembled.hip): re-sum the seam and slab-boundary rows of y = P x in PETSc AIJ
 // order after the stencil engine produced y (glo / ghi: x's ghost planes, nullptr on one rank)
 int launch_aij_seams(pb_grid* g, const Star& s, const double* x, const double* glo,

@@ -226,6 +226,61 @@ int pb_op_apply(pb_op* op, const pb_vec* x, pb_vec* y) {
   return op_apply_raw(op, x->d, y->d);
 }
 
+// ---------------------------------------------------------------------------------------------
+// MAC-grid gradient, projection and divergence of the 7-point operators (pb_mac.hip)
+// ---------------------------------------------------------------------------------------------
+// the checks the three calls share: the kind, the face field's three distinct vectors of the
+// operator's grid, the cell vector (another vector of that grid), a finite factor
+static int mac_check(const pb_op* op, const pb_vec* cell, const pb_vec* const f[3], double s) {
+  PB_CHECK_ARG(op && cell && f && f[0] && f[1] && f[2], "bad MAC args");
+  if (op->kind != PB_OP_STAR7 && op->kind != PB_OP_VARCOEF)
+    return set_error(PB_ERR_UNSUPPORTED,
+                     "the MAC operators need a PB_OP_STAR7 or PB_OP_VARCOEF operator");
+  PB_CHECK_ARG(cell->grid == op->grid, "vector/operator grid mismatch");
+  for (int d = 0; d < 3; ++d) {
+    PB_CHECK_ARG(f[d]->grid == op->grid, "vector/operator grid mismatch");
+    PB_CHECK_ARG(f[d] != cell, "the cell vector is one of the face field's components");
+  }
+  PB_CHECK_ARG(f[0] != f[1] && f[0] != f[2] && f[1] != f[2],
+               "the three components of a face field must be distinct vectors");
+  PB_CHECK_ARG(s - s == 0.0, "the factor s must be finite");
+  return PB_OK;
+}
+
+static int mac_grad(const pb_op* op, const pb_vec* p, double s, pb_vec* const u[3], bool project) {
+  PB_TRY(mac_check(op, p, u, s));
+  pb_grid* g = op->grid;
+  const MacCoef c = mac_coef_of(op);
+  double* const ud[3] = {u[0]->d, u[1]->d, u[2]->d};
+  const double* pd = p->d;
+  int none = 0;
+  return halo_overlap(g, pd, pd + (g->nzl - 1) * g->plane, wrap_planes(),
+                      project ? "mac_project" : "mac_grad", 0, &none,
+                      [&](int mode, const StencilPlanes& gp, int, int*) {
+                        return launch_mac_grad(g, c, pd, s, ud, project, gp, mode);
+                      });
+}
+
+int pb_op_mac_grad(const pb_op* op, const pb_vec* p, pb_vec* const g[3]) {
+  return mac_grad(op, p, 1.0, g, false);
+}
+
+int pb_op_mac_project(const pb_op* op, const pb_vec* p, double s, pb_vec* const u[3]) {
+  return mac_grad(op, p, s, u, true);
+}
+
+int pb_op_mac_div(const pb_op* op, double s, const pb_vec* const u[3], pb_vec* out) {
+  PB_TRY(mac_check(op, out, u, s));
+  pb_grid* g = op->grid;
+  const MacCoef c = mac_coef_of(op);
+  const double* const ud[3] = {u[0]->d, u[1]->d, u[2]->d};
+  int none = 0;
+  return halo_overlap(g, ud[2], ud[2] + (g->nzl - 1) * g->plane, wrap_planes(), "mac_div", 0, &none,
+                      [&](int mode, const StencilPlanes& gp, int, int*) {
+                        return launch_mac_div(g, c, s, ud, out->d, gp, mode);
+                      });
+}
+
 int pb_op_get_ownership_range(const pb_op* op, int64_t* first, int64_t* next) {
   PB_CHECK_ARG(op && first && next, "bad args");
   const pb_grid* g = op->grid;

@@ -35,7 +35,7 @@ namespace {
 const char* const kTuneNames[] = {
     "a2a_copy_self", "cg_defer_x", "engine_kc_skew", "cg_fold", "cg_fuse", "cg_sr_fused", "cheb_fused", "comm_mark_every",
     "comm_stall_test_ms", "compact_lines", "fft_rupd", "fgmres_fused", "pipecg_fused", "fft_zpad", "fft_zpad_min_plane",
-    "force_comm", "ksp_lazy0", "mg_agglomerate", "mg_engine_min_plane", "mg_poly_fused", "mg_restrict_z_min_cols",
+    "force_comm", "ksp_lazy0", "mac_wgcu", "mg_agglomerate", "mg_engine_min_plane", "mg_poly_fused", "mg_restrict_z_min_cols",
     "mg_split_fused", "mg_sweep2", "mg_tail_max", "mg_u4_split", "mg_varcoef_dinv_stored", "mg_varcoef_kc",
     "mg_varcoef_pre_fused", "pcr_lines", "rich_fused", "sor_omega_any", "sr_ddiff",
     "stencil_kc", "stencil_kc_skew", "stencil_nt", "stencil_tall", "stencil_wgcu", "varcoef_dot_fused", "varcoef_wgcu", "x_dot_cu"};

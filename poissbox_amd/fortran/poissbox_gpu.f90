@@ -115,6 +115,8 @@ module poissbox_gpu
   public :: assemble_laplacian
   public :: CompactGrad, CompactDiv, CompactInterp, CompactLapl, CompactLaplFast
   public :: CompactGradFast, CompactDivFast, CompactInterpFast
+  ! MAC-grid gradient, projection and divergence of the 7-point operators (pb_op_mac_*)
+  public :: MacGrad, MacProject, MacDiv
   ! C entry points on device pointers / host arrays (batched line solvers, compact operators)
   public :: c_pb_comm_unique_id, c_pb_tdma_batched, c_pb_tdma_sweeps_batched
   public :: c_pb_pcr_alpha_batched, c_pb_compact_1d_batched
@@ -217,6 +219,24 @@ module poissbox_gpu
           bind(C, name="pb_op_get_diagonal_vec")
        import :: c_int, c_ptr
        type(c_ptr), value :: op, diag
+     end function
+     ! MAC-grid G (cell to face) and D (face to cell) of PB_OP_STAR7 / PB_OP_VARCOEF: D G = A
+     integer(c_int) function c_pb_op_mac_grad(op, p, g) bind(C, name="pb_op_mac_grad")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: op, p
+       type(c_ptr), dimension(3) :: g
+     end function
+     integer(c_int) function c_pb_op_mac_project(op, p, s, u) bind(C, name="pb_op_mac_project")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: op, p
+       real(c_double), value :: s
+       type(c_ptr), dimension(3) :: u
+     end function
+     integer(c_int) function c_pb_op_mac_div(op, s, u, out) bind(C, name="pb_op_mac_div")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: op, out
+       real(c_double), value :: s
+       type(c_ptr), dimension(3) :: u
      end function
      ! src/tridsol.f90 on device pointers (element e of line l at ptr[l*line_stride + e*elem_stride])
      integer(c_int) function c_pb_tdma_batched(ctx, n, nbatch, ls, es, a, b, c, d, periodic) &
@@ -802,6 +822,43 @@ contains
     ierr = c_pb_compact_div(da%h, d, h, df%h)
     call check(ierr, "CompactDiv")
   end subroutine CompactDiv
+
+  !! MAC-grid operators of a 7-point Mat (PB_OP_STAR7, PB_OP_VARCOEF), split grids included:
+  !! g_d = G_d(p); u_d = u_d - s G_d(p) in place; out = s D(u). D G = A to rounding
+  subroutine MacGrad(A, p, g, ierr)
+    type(tMat), intent(in) :: A
+    type(tVec), intent(in) :: p
+    type(tVec), dimension(3), intent(inout) :: g
+    integer, intent(out) :: ierr
+    type(c_ptr), dimension(3) :: h
+    h = [g(1)%h, g(2)%h, g(3)%h]
+    ierr = c_pb_op_mac_grad(A%h, p%h, h)
+    call check(ierr, "MacGrad")
+  end subroutine MacGrad
+
+  subroutine MacProject(A, p, s, u, ierr)
+    type(tMat), intent(in) :: A
+    type(tVec), intent(in) :: p
+    real(pb_dp), intent(in) :: s
+    type(tVec), dimension(3), intent(inout) :: u
+    integer, intent(out) :: ierr
+    type(c_ptr), dimension(3) :: h
+    h = [u(1)%h, u(2)%h, u(3)%h]
+    ierr = c_pb_op_mac_project(A%h, p%h, real(s, c_double), h)
+    call check(ierr, "MacProject")
+  end subroutine MacProject
+
+  subroutine MacDiv(A, s, u, out, ierr)
+    type(tMat), intent(in) :: A
+    real(pb_dp), intent(in) :: s
+    type(tVec), dimension(3), intent(in) :: u
+    type(tVec), intent(inout) :: out
+    integer, intent(out) :: ierr
+    type(c_ptr), dimension(3) :: h
+    h = [u(1)%h, u(2)%h, u(3)%h]
+    ierr = c_pb_op_mac_div(A%h, real(s, c_double), h, out%h)
+    call check(ierr, "MacDiv")
+  end subroutine MacDiv
 
   subroutine CompactInterp(da, stagger, f, fi, ierr)
     type(tDM), intent(in) :: da
